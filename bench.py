@@ -11,11 +11,15 @@ Launch: `python bench.py --gpus N` starts N ranks ITSELF (one process per GPU th
 xGMI) when it is not already running under a launcher; under `python -m torch.distributed.run ... bench.py --gpus N` it
 joins the existing rendezvous.  A world size different from --gpus is an error, never a silent 1-rank run.
 
-One JSON line on rank 0.  Extra objects:
+One JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = wall
+milliseconds of one timed step).  `--dump-outputs DIR` then also writes what the last timed step computed (see
+dump_outputs).  `--full` adds the side measurements below; they cost runs of their own and are off by default:
   roofline     all conv MFMA launches (Winograd, implicit-GEMM gather / LDS-patch, weight gradient), HIP-event timed on
                the launch stream inside the timed steps.  `achieved` = EXECUTED MFMA FLOP/s (algorithmic direct-conv
                FLOPs on the unpadded domain; Winograd launches divided by their 2.25x multiply reduction) against the
                fp32 matrix peak; per-family and whole-step figures beside it.
+  side_configs the bf16 BASELINE configurations as HIP-graph replays after the headline region (1 GPU, configs[1] only)
+  hip_graph_replay  configs[2-4]: the same step as HIP-graph replays after the eager timed region
   cpu_baseline the CPU oracle (oracle/c2m_oracle.py, validated bit-exact against the reference) timed on this host
 """
 import argparse
@@ -25,7 +29,9 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -226,6 +232,79 @@ def _family(s, names, divide=1.0, peak=PEAK_FP32_MFMA_TFLOPS, step_s=None):
             "share_of_step_time": round(ms * 1e-3 / step_s, 3) if step_s else None}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_GRAD_SAMPLE = 1 << 20        # gradient elements kept (seeded sample over all parameters)
+
+
+def _tensors(prefix, obj, out):
+    """Every tensor in a nest of dicts / lists / tuples, keyed by its path ('out.generated', 'loss.kl', ...)."""
+    if torch.is_tensor(obj):
+        out[prefix] = obj
+    elif isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _tensors(f"{prefix}.{k}", obj[k], out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _tensors(f"{prefix}.{i}", v, out)
+
+
+def _sample(flat, cap, name):
+    """All of `flat` if it has at most `cap` elements, else `cap` of them at indices drawn from a generator seeded by `name`
+    (the same indices in every run, so two builds compare element for element)."""
+    n = flat.numel()
+    if n <= cap:
+        return flat
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    idx = torch.randint(n, (cap,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(directory, result, model):
+    """What a caller of the timed step receives from its last step, as DIR/<name>.npy: every tensor of the generated dict
+    (out.*) and of the loss dicts (loss.*, loss_d.*), float32 (float64 for integer tensors, so indices stay exact); the
+    parameter gradients as grad_norms.npy (float64 L2 norm of every gradient the step left, in named_parameters() order;
+    parameters the step does not train, such as the discriminators of a generator-only step, have none and are not listed)
+    and grad_sample.npy (float32, a seeded sample of DUMP_GRAD_SAMPLE elements of those gradients).
+    Arrays larger than their share of DUMP_BUDGET_BYTES are seeded samples; the files total at most that budget."""
+    generated, loss_g, loss_d = result
+    arrays = {}
+    _tensors("out", generated, arrays)
+    _tensors("loss", loss_g, arrays)
+    _tensors("loss_d", loss_d, arrays)
+    grads = [p.grad for p in model.parameters() if p.grad is not None]
+    total = sum(g.numel() for g in grads)
+    per_array = (DUMP_BUDGET_BYTES - 4 * DUMP_GRAD_SAMPLE - 8 * len(grads)) // max(1, len(arrays))
+    os.makedirs(directory, exist_ok=True)
+    written = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float32 if (t.is_floating_point() or t.dtype == torch.bool) else torch.float64
+        flat = _sample(t.reshape(-1), per_array // (4 if dt == torch.float32 else 8), name)
+        a = flat.to(dt).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written += a.nbytes
+    norms = np.array([float(g.double().norm()) for g in grads], np.float64)
+    np.save(os.path.join(directory, "grad_norms.npy"), norms)
+    if grads:
+        # sample over the concatenation of all gradients without materialising it: sorted global indices, split per parameter
+        g = torch.Generator().manual_seed(zlib.crc32(b"grad_sample"))
+        k = min(total, DUMP_GRAD_SAMPLE)
+        idx = torch.arange(total) if k == total else torch.randint(total, (k,), generator=g).sort().values
+        bounds = torch.tensor([0] + [x.numel() for x in grads]).cumsum(0)
+        pos = torch.searchsorted(idx, bounds).tolist()
+        parts = []
+        for i, gr in enumerate(grads):
+            if pos[i + 1] > pos[i]:
+                sel = idx[pos[i]:pos[i + 1]] - bounds[i]
+                parts.append(gr.detach().reshape(-1)[sel.to(gr.device)].float().cpu())
+        sample = torch.cat(parts).numpy()
+        np.save(os.path.join(directory, "grad_sample.npy"), sample)
+        written += sample.nbytes
+    written += norms.nbytes
+    assert written <= DUMP_BUDGET_BYTES, written
+    return written
+
+
 def side_config(k, dev, steps=10, warmup=3):
     """One of the bf16 BASELINE configurations (2: 256x512 B4, 3: 128x256 B8; full adversarial step) measured in THIS process after
     (and outside) the headline timed region: `warmup` eager steps, one eager step with HIP events around every conv launch (the conv
@@ -305,9 +384,14 @@ def main():
                     help="7-frame windows per stream sample (2 = BASELINE configs[4]'s 14-frame streams); clips/GPU = batch x windows")
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (roofline, side_configs, hip_graph_replay of configs 2-4, cpu_baseline); "
+                         "a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--conv-table", default=None, help="write a per-shape conv timing table to this file")
+    ap.add_argument("--conv-table", default=None, help="write a per-shape conv timing table to this file (needs --full)")
     ap.add_argument("--event-every", type=int, default=10,
                     help="the HIP events around every conv launch (roofline object) are recorded in every k-th step of the timed "
                          "region.  Those steps time ISOLATED launches: the branch streams of ops.aux_branch / ops.deferred_wgrads are "
@@ -323,7 +407,8 @@ def main():
                     help="side measurement: capture zero_grad + forward + backward into a HIP graph and time replays (no "
                          "per-kernel events, so no roofline object; with N > 1 the all-reduces run eagerly after each replay)")
     ap.add_argument("--graph-side", dest="graph_side", action="store_true", default=None,
-                    help="also time HIP-graph replays of the step after the eager timed region (default: on for configs 2-4)")
+                    help="also time HIP-graph replays of the step after the eager timed region (default: on for configs 2-4 "
+                         "with --full)")
     ap.add_argument("--no-graph-side", dest="graph_side", action="store_false")
     ap.add_argument("--fp32-allreduce", action="store_true",
                     help="keep fp32 gradient buckets on the wire in the bf16 configurations (default there: bf16 copies)")
@@ -334,11 +419,15 @@ def main():
                     help="run the bucketed RCCL all-reduce path even with one rank (plumbing check on a single GPU)")
     ap.add_argument("--side-configs", default=None,
                     help="comma-separated BASELINE configs measured as HIP-graph replays in the same process AFTER the headline timed "
-                         "region and reported as `side_configs` (default: '3,2' for the plain 1-GPU configs[1] run, '' otherwise)")
+                         "region and reported as `side_configs` (default: '3,2' for the 1-GPU configs[1] run with --full, '' otherwise)")
     ap.add_argument("--side-steps", type=int, default=10)
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-index", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.conv_table and not (args.full and not args.no_roofline):
+        ap.error("--conv-table comes from the roofline events: needs --full (and no --no-roofline)")
     if args.cpu_worker:
         return _cpu_worker(args.cpu_worker, args.height or 128, args.width or 256, args.cpu_worker_index)
     for k, v in CONFIGS[args.config].items():
@@ -386,7 +475,7 @@ def main():
     import contextlib
     # configs[2-4] (full adversarial step, ~2000 launches): the eager line is partly host-bound, so the same run also times
     # HIP-graph replays of zero_grad + forward + backward (+ eager optimizers / all-reduce) as a side object
-    graph_side = args.graph_side if args.graph_side is not None else (args.config != 1 and not args.graph)
+    graph_side = args.graph_side if args.graph_side is not None else (args.full and args.config != 1 and not args.graph)
     gctx = torch.cuda.stream(step.graph_stream) if (args.graph or graph_side) else contextlib.nullcontext()
     graph_side_result = None
     with gctx:                                  # with --graph every step (eager warm-up included) runs on the capture stream
@@ -399,17 +488,19 @@ def main():
         if step.reducer is not None:
             step.reducer.reset_measurements()
         barrier()
-        prof = None if args.no_roofline else ops.ConvProfiler()
+        prof = None if (args.no_roofline or not args.full) else ops.ConvProfiler()
         t0 = time.perf_counter()
         sampled = 0
         for i in range(args.steps):
             on = prof is not None and i % max(args.event_every, 1) == 0
             ops.ConvProfiler.active = prof if on else None
             sampled += int(on)
-            step(batch)
+            last = step(batch)
         ops.ConvProfiler.active = None
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:       # before the replays below: with optimizers on they move the weights
+            dump_outputs(args.dump_outputs, last, model)
         if graph_side:
             step.capture(batch)
             step(batch)
@@ -543,7 +634,7 @@ def main():
                     f.write(f"{tag} | {n / sampled:.1f} {ms / sampled:.3f} {tf:.1f}\n")
         side = args.side_configs
         if side is None:
-            side = "3,2" if (world == 1 and args.config == 1 and not args.graph and not args.force_reducer and
+            side = "3,2" if (args.full and world == 1 and args.config == 1 and not args.graph and not args.force_reducer and
                              (args.batch, args.windows, args.height, args.width, args.dtype) == (8, 1, 128, 256, "f32")) else ""
         if side and world == 1:
             # the bf16 configurations, outside the timed region (after it): the headline objects must not hold HBM while they run
@@ -558,7 +649,7 @@ def main():
                     result["side_configs"][f"configs[{k}]"] = side_config(k, dev, steps=args.side_steps)
                 except Exception as e:                     # a side measurement never takes the headline line down
                     result["side_configs"][f"configs[{k}]"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(bench_config(args.height, args.width, False))
         print(json.dumps(result), flush=True)
     if dist.is_initialized():

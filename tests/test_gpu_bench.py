@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ def _json_line(out):
 
 
 def test_bench_single_process_contract():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--batch", "1", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)
@@ -31,6 +32,36 @@ def test_bench_single_process_contract():
     for fam in rf["families"].values():
         assert 0 < fam["frac"] < 1, fam                             # every family is priced against the MFMA pipe it runs on
     assert r["rccl_ranks"] == 0 and "config" in r and "BASELINE configs[1]" in r["config"]["workload"]
+
+
+def test_bench_plain_run_times_only_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run (no --full) prints the headline keys and none of the side measurements; --dump-outputs writes the last timed
+    step's outputs, losses and gradients as float32 / float64 .npy files within 64 MB, the same bits in two runs."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--batch", "1", "--dump-outputs", str(d)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        r = _json_line(out.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in r, k
+        assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["unit"] == "frames/s" and r["higher_is_better"] is True
+        assert abs(r["value"] - 7 * 1000.0 / r["ms_per_step"]) < 0.01 * r["value"]
+        for k in ("roofline", "side_configs", "cpu_baseline"):
+            assert k not in r, k
+        assert r["hip_graph_replay"] is None
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for f in ("out.generated.npy", "loss.total_gen.npy", "grad_norms.npy", "grad_sample.npy"):
+        assert f in a, (f, sorted(a))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), (f, a[f].dtype)
+        assert np.isfinite(a[f]).all(), f
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+    assert a["grad_norms.npy"].max() > 0
 
 
 def test_bench_refuses_a_world_size_that_is_not_gpus():
@@ -107,7 +138,7 @@ def test_two_rank_rccl_bench_when_two_gpus_are_visible():
 def test_bench_baseline_config_presets(config, expect):
     """`--config K` runs BASELINE.json configs[K] (here at batch 1 to stay short): resolution, bf16 conv mode, both
     discriminators + the four Adam steps, and for configs[4] two 7-frame windows per stream sample."""
-    out = subprocess.run([sys.executable, "bench.py", "--config", str(config), "--batch", "1", "--steps", "1", "--warmup", "1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--config", str(config), "--batch", "1", "--steps", "1", "--warmup", "1",
                           "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _json_line(out.stdout)

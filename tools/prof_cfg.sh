@@ -6,10 +6,10 @@ C=${1:-3}
 TAG=${2:-r03}
 O=$PWD/gpurun_out/$TAG/cfg$C
 mkdir -p $O
-python3 bench.py --config $C --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || tail -3 $O/bench.err
+python3 bench.py --full --config $C --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || tail -3 $O/bench.err
 echo "bench done"
 rm -rf $O/trace
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --config $C --steps 5 --warmup 2 --no-cpu-baseline --no-graph-side --conv-table $O/conv_shape_table.txt > $O/trace.log 2>&1 || tail -5 $O/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --config $C --steps 5 --warmup 2 --no-cpu-baseline --no-graph-side --conv-table $O/conv_shape_table.txt > $O/trace.log 2>&1 || tail -5 $O/trace.log
 cp $O/trace/*/*kernel_stats.csv $O/kernel_stats.csv
 rm -rf $O/trace
 echo "trace done"
