@@ -5,6 +5,7 @@
 //                              "* occlusion" (motion_autoencoder.py:125, model.py:208).
 //   c2m_upsample2x_fwd / _bwd  nn.Upsample(scale_factor=2, bilinear) (up_block.py:10, generator.py:77)
 //   c2m_resize_bilinear        F.interpolate(size, bilinear) both align modes (utils.py:349, motion_autoencoder.py:123)
+//   c2m_resize_bilinear_bwd    its backward (size-given calls), gather form: the odd-frame-size skip sites
 //   c2m_maxpool2x2_fwd / _bwd  VGG-19 pools (vgg.py via torchvision features 4,9,18,27)
 //
 // This file is compiled with -ffp-contract=off: the coordinate arithmetic follows the exact fp32 operation order
@@ -447,6 +448,100 @@ C2M_API int c2m_resize_bilinear(const void* in, void* out, long NC, int Hi, int 
                                 double scale_factor, int dt, void* stream) {
     C2M_ENTER();
     return resize_bilinear_launch(in, out, NC, Hi, Wi, Ho, Wo, align, scale_factor, dt, stream);
+}
+
+// Adjoint of resize_bilinear_kernel (size-given call), gather form: one thread per INPUT pixel sums, in a fixed order, the
+// output pixels whose taps reach it -- no float atomics (ATen's GPU backward scatters with them), every run the same bits.
+// lerp_src(o).i0 is monotone in o, so the outputs whose i0 or i1 is input row y are the contiguous range {o : i0(o) in
+// [y-1, y]}; the same holds per column.  The range ends come from a float estimate corrected with lerp_src itself, so the
+// weights are the forward's bit for bit (this file is compiled with -ffp-contract=off).
+// first output index o in [0, out] with lerp_src(o).i0 >= t
+__device__ __forceinline__ int resize_first_out(int t, int in, int out, float scale, bool align) {
+    if (t <= 0) return 0;
+    if (t > in - 1 || scale <= 0.0f) return out;                 // i0 <= in - 1; scale 0: every i0 is 0
+    const float est = align ? (float)t / scale : ((float)t + 0.5f) / scale - 0.5f;
+    int o = est <= 0.0f ? 0 : (est >= (float)out ? out : (int)ceilf(est));
+    while (o > 0 && lerp_src(o - 1, in, scale, align).i0 >= t) --o;
+    while (o < out && lerp_src(o, in, scale, align).i0 < t) ++o;
+    return o;
+}
+
+// The outputs of one axis that reach input index v: [o0, o0 + n) with their weights when n <= RB_TAPS (every ratio up to
+// about 2x up-sampling), else n only.  An axis whose extent does not change is the identity (scale 1: lerp_src(v) = (v, v
+// or v + 1, 1, 0)); its one tap of weight 1 is exactly what the generic range yields once the zero weight is skipped.
+constexpr int RB_TAPS = 4;
+struct RbTaps { int o0, n; float w[RB_TAPS]; };
+__device__ __forceinline__ float rb_weight(int o, int v, int in, float scale, bool al) {
+    const Lerp l = lerp_src(o, in, scale, al);
+    return (l.i0 == v ? l.l0 : 0.0f) + (l.i1 == v ? l.l1 : 0.0f);
+}
+__device__ __forceinline__ RbTaps rb_taps(int v, int in, int out, float scale, bool al) {
+    RbTaps t;
+    if (in == out) {
+        t.o0 = v; t.n = 1; t.w[0] = 1.0f;
+#pragma unroll
+        for (int k = 1; k < RB_TAPS; ++k) t.w[k] = 0.0f;
+        return t;
+    }
+    t.o0 = resize_first_out(v - 1, in, out, scale, al);
+    t.n = resize_first_out(v + 1, in, out, scale, al) - t.o0;
+#pragma unroll
+    for (int k = 0; k < RB_TAPS; ++k) t.w[k] = k < t.n ? rb_weight(t.o0 + k, v, in, scale, al) : 0.0f;
+    return t;
+}
+
+template <typename I, class T = float>
+__global__ __launch_bounds__(256) void resize_bilinear_bwd_kernel(const T* __restrict__ gout, T* __restrict__ gin, long NC,
+                                                                  int Hi, int Wi, int Ho, int Wo, float sh, float sw, int align) {
+    const I total = (I)(NC * Hi * Wi);
+    const bool al = align != 0;
+    for (I i = blockIdx.x * (I)blockDim.x + threadIdx.x; i < total; i += (I)gridDim.x * blockDim.x) {
+        const int x = (int)(i % (I)Wi); const I r = i / (I)Wi;
+        const int y = (int)(r % (I)Hi); const I nc = r / (I)Hi;
+        const T* __restrict__ g = gout + (long)nc * Ho * Wo;
+        const RbTaps ty = rb_taps(y, Hi, Ho, sh, al), tx = rb_taps(x, Wi, Wo, sw, al);
+        float acc = 0.0f;
+        if (ty.n <= RB_TAPS && tx.n <= RB_TAPS) {
+#pragma unroll
+            for (int a = 0; a < RB_TAPS; ++a) {
+                if (ty.w[a] == 0.0f) continue;
+                const T* __restrict__ grow = g + (long)(ty.o0 + a) * Wo + tx.o0;
+                float row = 0.0f;
+#pragma unroll
+                for (int b = 0; b < RB_TAPS; ++b)
+                    if (tx.w[b] != 0.0f) row += tx.w[b] * c2m_ld(grow, b);
+                acc += ty.w[a] * row;
+            }
+        } else {              // strong up-sampling: weights recomputed per tap, same order and skips as above
+            for (int oy = ty.o0; oy < ty.o0 + ty.n; ++oy) {
+                const float wy = rb_weight(oy, y, Hi, sh, al);
+                if (wy == 0.0f) continue;
+                const T* __restrict__ grow = g + (long)oy * Wo;
+                float row = 0.0f;
+                for (int ox = tx.o0; ox < tx.o0 + tx.n; ++ox) {
+                    const float wx = rb_weight(ox, x, Wi, sw, al);
+                    if (wx != 0.0f) row += wx * c2m_ld(grow, ox);
+                }
+                acc += wy * row;
+            }
+        }
+        c2m_st(gin, (long)i, acc);
+    }
+}
+
+C2M_API int c2m_resize_bilinear_bwd(const void* gout, void* gin, long NC, int Hi, int Wi, int Ho, int Wo, int align, int dt,
+                                    void* stream) {
+    C2M_ENTER();
+    if (Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || NC < 0) return (int)hipErrorInvalidValue;
+    const long total = NC * Hi * Wi;
+    if (total <= 0) return 0;
+    const float sh = area_scale(Hi, Ho, align, 0.0), sw = area_scale(Wi, Wo, align, 0.0);
+    const dim3 grid(c2m_grid(total, 256));
+    hipStream_t s = (hipStream_t)stream;
+    C2M_DISPATCH_DT(dt,
+        if (total < (1L << 31)) hipLaunchKernelGGL((resize_bilinear_bwd_kernel<unsigned, T>), grid, dim3(256), 0, s, (const T*)gout, (T*)gin, NC, Hi, Wi, Ho, Wo, sh, sw, align);
+        else hipLaunchKernelGGL((resize_bilinear_bwd_kernel<long, T>), grid, dim3(256), 0, s, (const T*)gout, (T*)gin, NC, Hi, Wi, Ho, Wo, sh, sw, align););
+    return (int)hipGetLastError();
 }
 
 // x2 upsample (align_corners=False; up_block.py:10): one thread per INPUT pixel writes its 2x2 outputs as two 8-byte

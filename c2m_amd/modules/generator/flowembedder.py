@@ -3,6 +3,7 @@
 import torch
 from torch import nn
 
+from ... import ops
 from ..layers.same_block import SameBlock2d
 from ..layers.down_block import DownBlock2d
 from ..layers.up_block import UpBlock2d
@@ -43,8 +44,8 @@ class FlowEmbedder(nn.Module):
         dec, cur = [], enc[-1]
         for i in reversed(range(nd)):
             if i != nd - 1:
-                if cur.shape[-2:] != enc[i + 1].shape[-2:]:
-                    raise NotImplementedError("FlowEmbedder skip/upsample size mismatch (odd input extents)")
+                if cur.shape[-2:] != enc[i + 1].shape[-2:]:       # odd extents (flowembedder.py:72-74)
+                    cur = ops.resize_bilinear_grad(cur, enc[i + 1].shape[-2:])
                 cur = torch.cat([cur, enc[i + 1]], dim=1)
             cur = self.up_blocks[i](cur)
             dec.append(cur)

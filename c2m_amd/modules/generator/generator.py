@@ -111,13 +111,13 @@ class OcclusionAwareGenerator(nn.Module):
         for i, blk in enumerate(self.up_blocks):
             if self.use_spade:
                 c = cond[nd - i]
-                if out.shape[-2:] != c[0].shape[-2:]:
-                    raise NotImplementedError("generator feature/conditioning size mismatch")
+                if out.shape[-2:] != c[0].shape[-2:]:            # odd extents: to the conditioning size (generator.py:148-150)
+                    out = ops.resize_bilinear_grad(out, c[0].shape[-2:])
                 out = ops.upsample2x(blk(out, *c))
             else:
                 out = blk(out)
-        if out.shape[-2:] != first_frame.shape[-2:]:
-            raise NotImplementedError("generator output size mismatch (input extents must be divisible by 8)")
+        if out.shape[-2:] != first_frame.shape[-2:]:            # to the frame size before the 7x7 head (generator.py:155-156)
+            out = ops.resize_bilinear_grad(out, first_frame.shape[-2:])
         return conv_module(out, self.final[0], act="sigmoid")
 
 

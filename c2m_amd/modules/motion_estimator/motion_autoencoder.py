@@ -112,9 +112,11 @@ class DenseMotionDecoder(nn.Module):
 
     @staticmethod
     def _match(x5, hw):
+        """utils.resize_video(x, [h, w], mode="bilinear") where the up-sampled map and its skip disagree (odd extents,
+        motion_autoencoder.py:128-130,138-140): every [h, w] plane of the contiguous 5-D map resized in one launch."""
         if list(x5.shape[-2:]) == list(hw):
             return x5
-        raise NotImplementedError("feature-map size mismatch in DenseMotionDecoder (needs a differentiable resize)")
+        return ops.resize_bilinear_grad(x5, hw)
 
     def forward(self, appearance_features, sparse_features, sparse_motion, sparse_occlusion, z):
         T, nu = self.num_predicted_frames, self.num_up_blocks

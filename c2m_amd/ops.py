@@ -2294,6 +2294,46 @@ def resize_bilinear(x, size, align_corners=False):
     return y
 
 
+class _ResizeBilinearFn(torch.autograd.Function):
+    """Every leading dimension is a plane: a contiguous [B,C,T,H,W] is B*C*T planes, so the reference's fold -> interpolate
+    -> unfold (utils.resize_video) is this one launch with no permute copies."""
+
+    @staticmethod
+    def forward(ctx, x, Ho, Wo, align):
+        x = _f(x)
+        H, W = x.shape[-2:]
+        planes = x.numel() // max(H * W, 1)
+        y = torch.empty(x.shape[:-2] + (Ho, Wo), device=x.device, dtype=x.dtype)
+        ctx.meta = (x.shape, planes, H, W, Ho, Wo, align)
+        _lib.check(_lib.lib().c2m_resize_bilinear(_p(x), _p(y), planes, H, W, Ho, Wo, align, 0.0, _dt(x), _stream()),
+                   "resize_bilinear")
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        shape, planes, H, W, Ho, Wo, align = ctx.meta
+        gy = _f(gy)
+        gx = torch.empty(shape, device=gy.device, dtype=gy.dtype)
+        _lib.check(_lib.lib().c2m_resize_bilinear_bwd(_p(gy), _p(gx), planes, H, W, Ho, Wo, align, _dt(gy), _stream()),
+                   "resize_bilinear_bwd")
+        return gx, None, None, None
+
+
+def resize_bilinear_grad(x, size, align_corners=False):
+    """Differentiable F.interpolate(x, size, mode='bilinear') of a 4-D [N,C,H,W] or 5-D [B,C,T,H,W] tensor (each H x W
+    plane resized).  The forward is c2m_resize_bilinear (the same bits as resize_bilinear), the backward its gather-form
+    adjoint c2m_resize_bilinear_bwd (no atomics: repeatable bit for bit).  Returns x itself when the size already matches."""
+    _dev(x)
+    if x.dim() not in (4, 5):
+        raise ValueError(f"resize_bilinear_grad takes 4-D or 5-D tensors, got {x.dim()}-D")
+    Ho, Wo = int(size[0]), int(size[1])
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"resize_bilinear_grad: output size {Ho}x{Wo}")
+    if tuple(x.shape[-2:]) == (Ho, Wo):
+        return x
+    return _ResizeBilinearFn.apply(x, Ho, Wo, 1 if align_corners else 0)
+
+
 class _MaxPool2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

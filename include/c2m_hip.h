@@ -285,6 +285,10 @@ int c2m_flow_warp_bwd(const void* img, const float* flow, const float* occ, cons
 /* F.interpolate(bilinear) (utils/utils.py:349 align_corners=True; motion_autoencoder.py:123, up_block.py:10).  */
 int c2m_resize_bilinear(const void* in, void* out, long NC, int Hi, int Wi, int Ho, int Wo, int align,
                         double scale_factor, int dt, void* stream);
+/* adjoint of the size-given c2m_resize_bilinear (any Hi, Wi, Ho, Wo >= 1, both align modes): gin [NC][Hi][Wi] from
+ * gout [NC][Ho][Wo].  Gathers per input pixel in a fixed order (no float atomics, no zero-initialisation of gin).   */
+int c2m_resize_bilinear_bwd(const void* gout, void* gin, long NC, int Hi, int Wi, int Ho, int Wo, int align, int dt,
+                            void* stream);
 int c2m_upsample2x_fwd(const void* in, void* out, long NC, int Hi, int Wi, int dt, void* stream);
 /* The same up-sampling (up_block.py:10) from an NC8 tensor to an NC8 tensor ([N*ceil(C/8)][H][W][8] bf16 -> [..][2H][2W][8]), for the
  * up block whose convolution reads the channel-blocked form only (round 4); per channel the arithmetic of c2m_upsample2x_fwd. */
