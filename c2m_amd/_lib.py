@@ -60,6 +60,8 @@ _SIGS = {
     "c2m_prep_video": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "c2m_prep_seg_onehot": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "c2m_prep_flow_occ": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "c2m_instance_stats": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "c2m_instance_compact": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "c2m_event_create": (c_int, [c_void_p]),
     "c2m_event_record": (c_int, [c_void_p, c_void_p]),
     "c2m_event_elapsed_ms": (c_int, [c_void_p, c_void_p, c_void_p]),

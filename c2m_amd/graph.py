@@ -52,12 +52,23 @@ def scene_graph(tracks, size, num_input_frames, num_frames, lambda_traj=1):
     Node features: [cy, cx] in [-1,1], [h, w] as image fractions, one-hot(19) of id // 1000 (ids >= 19000 raise
     IndexError like np.eye(19)[...] does).  targets_theta[n, t] = [sx, 0, dx, 0, sy, dy] relative to the LAST input
     frame.  lambda_traj > 1 stretches the horizontal displacement of the target frames (:126-141)."""
-    H, W = size
-    t_in = num_input_frames
     if not tracks:
         raise ValueError("a scene needs at least one tracked instance (the reference cannot collate an empty graph)")
     box, ids = parse_tracks(tracks, num_frames)
+    return scene_graph_from_boxes(box, ids, size, num_input_frames, num_frames, lambda_traj)
+
+
+def scene_graph_from_boxes(box, ids, size, num_input_frames, num_frames, lambda_traj=1):
+    """The arithmetic of scene_graph on parsed boxes: box [N,T,4] float64 (x, y, w, h in the tracker's 2048x1024 pixels),
+    ids [N,T] int64, T = num_frames.  Returns (tracking_ids [T,N] int64, GraphData), as scene_graph does."""
+    H, W = size
+    t_in = num_input_frames
+    box, ids = np.asarray(box, dtype=np.float64), np.asarray(ids, dtype=np.int64)
+    if box.ndim != 3 or box.shape[2] != 4 or ids.shape != box.shape[:2] or box.shape[0] < 1:
+        raise ValueError(f"need box [N,T,4] and ids [N,T] with N >= 1, got {box.shape} and {ids.shape}")
     N, T = ids.shape
+    if T != num_frames:
+        raise ValueError(f"boxes cover {T} frames, num_frames={num_frames}")
     if not 1 <= t_in < T:
         raise ValueError("need 1 <= num_input_frames < num_frames")
     x_l = box[..., 0] / 2048 * W

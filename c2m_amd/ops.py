@@ -2452,6 +2452,73 @@ def sparse_raster(instance, obj_id, obj_batch, thetas):
     return bw, fw, binm
 
 
+def _instance_input(instance, num_input_frames):
+    """[B,1,T,H,W] or [B,T,H,W] integer ids on the device -> contiguous int32 [B,T,H,W] (no copy for an int32 input)."""
+    if not instance.is_cuda:
+        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if instance.dim() == 5:
+        if instance.shape[1] != 1:
+            raise ValueError(f"instance maps must be [B,1,T,H,W] or [B,T,H,W], got {tuple(instance.shape)}")
+        instance = instance[:, 0]
+    if instance.dim() != 4:
+        raise ValueError(f"instance maps must be [B,1,T,H,W] or [B,T,H,W], got {tuple(instance.shape)}")
+    if instance.dtype.is_floating_point or instance.dtype == torch.bool or instance.is_complex():
+        raise TypeError(f"instance maps hold integer ids, got {instance.dtype}")
+    if not 1 <= num_input_frames <= instance.shape[1]:
+        raise ValueError(f"num_input_frames={num_input_frames} but the maps have {instance.shape[1]} frames")
+    if instance.device.index != _cur_device():
+        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{instance.device.index} but the current device is "
+                           f"cuda:{_cur_device()}")
+    return _f(instance if instance.dtype == torch.int32 else instance.to(torch.int32))
+
+
+def instance_stats(instance, num_input_frames, id_range=(1000, 19000)):
+    """Per-instance pixel statistics of the first `num_input_frames` frames: int32 [B, t_in, id_hi - id_lo, 5] on the device,
+    (count, x_min, x_max, y_min, y_max) of every id in [id_lo, id_hi) (an absent id: count 0, x_min = y_min = 2**31 - 1,
+    x_max = y_max = -1).  Integer atomics only: the table is the same on every run."""
+    inst = _instance_input(instance, num_input_frames)
+    id_lo, id_hi = (int(v) for v in id_range)
+    if not 0 <= id_lo < id_hi:
+        raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
+    B, T, H, W = inst.shape
+    table = torch.empty(B, num_input_frames, id_hi - id_lo, 5, device=inst.device, dtype=torch.int32)
+    _lib.check(_lib.lib().c2m_instance_stats(_p(inst), _p(table), B, T, num_input_frames, H, W, id_lo, id_hi, _stream()),
+               "instance_stats")
+    return table
+
+
+def instance_boxes(instance, num_input_frames, id_range=(1000, 19000), min_pixels=1, max_nodes=64):
+    """The objects of every sample: ids in `id_range` that cover >= `min_pixels` pixels in EACH of the first
+    `num_input_frames` frames, in ascending id order, with their pixel boxes per input frame.
+
+    instance: [B,1,T,H,W] or [B,T,H,W] integer ids on the device.  The default range is the rule of
+    graph.scene_graph: class id // 1000 < 19, ids below 1000 are stuff / background.
+    Returns CPU tensors (one device -> host read; the graph size depends on the data):
+      ids [B, max_nodes] int32, boxes [B, max_nodes, t_in, 4] int32 (x_min, y_min, x_max + 1, y_max + 1: pixel edges),
+      count [B] int32; slots past count[b] are zero.  More than `max_nodes` objects in a sample raises ValueError."""
+    t_in = int(num_input_frames)
+    min_pixels, max_nodes = int(min_pixels), int(max_nodes)
+    if min_pixels < 1 or max_nodes < 1:
+        raise ValueError("min_pixels and max_nodes must be >= 1")
+    table = instance_stats(instance, t_in, id_range)
+    B, nid = table.shape[0], table.shape[2]
+    n_ids, n_box = B * max_nodes, B * max_nodes * t_in * 4
+    out = torch.empty(n_ids + n_box + 2 * B, device=table.device, dtype=torch.int32)
+    ids, boxes = out[:n_ids], out[n_ids:n_ids + n_box]
+    count, overflow = out[n_ids + n_box:n_ids + n_box + B], out[n_ids + n_box + B:]
+    if B:
+        _lib.check(_lib.lib().c2m_instance_compact(_p(table), _p(ids), _p(boxes), _p(count), _p(overflow), B, t_in, nid,
+                                                   int(id_range[0]), min_pixels, max_nodes, _stream()), "instance_compact")
+    host = out.cpu()
+    ids, boxes = host[:n_ids].view(B, max_nodes), host[n_ids:n_ids + n_box].view(B, max_nodes, t_in, 4)
+    count, overflow = host[n_ids + n_box:n_ids + n_box + B], host[n_ids + n_box + B:]
+    bad = overflow.nonzero().flatten().tolist()
+    if bad:
+        raise ValueError(f"sample(s) {bad} hold more than max_nodes={max_nodes} objects; the object graph is complete "
+                         "(N*(N-1) edges), raise max_nodes or min_pixels")
+    return ids, boxes, count
+
+
 def occlusion_splat(flow, want_map=True, want_clip=False):
     """get_occlusion_map for [B,2,H,W] or, frame-batched, [B,2,T,H,W] flows -> ([B,1,(T,)H,W] map, clip_mask) ."""
     _dev(flow)

@@ -368,6 +368,19 @@ int c2m_prep_seg_onehot(const uint8_t* labels_bthw, float* bg_mask, float* fg_ma
 int c2m_prep_flow_occ(const uint8_t* occ_bthw, const float* flow_bthwc, float* occ_out, float* flow_out, int B, int T,
                       int H, int W, void* stream);
 
+/* Per-instance boxes of the input frames, for graphs built from instance maps instead of tracker files (click-to-move;
+ * c2m_amd.interactive).  The reference has no counterpart: it reads per-object tracker boxes (cityscapes.py:79-199).
+ * c2m_instance_stats: instance [B][T][H][W] int32, planes = (sample, input frame t < t_in); for every id in [id_lo, id_hi)
+ *   (id_lo >= 0; other ids are ignored) table[B*t_in][id_hi-id_lo][5] = {count, x_min, x_max, y_min, y_max} (an absent id:
+ *   {0, INT_MAX, -1, INT_MAX, -1}).  The table is written in full; integer atomics only, so the result is bit-repeatable.
+ * c2m_instance_compact: per sample, the ids with count >= min_pixels (>= 1) in EVERY input frame, ascending:
+ *   ids[B][max_nodes], boxes[B][max_nodes][t_in][4] = {x_min, y_min, x_max+1, y_max+1}, count[B] (<= max_nodes),
+ *   overflow[B] = 1 when the sample has more than max_nodes such ids.  Slots past count are zero; no atomics.      */
+int c2m_instance_stats(const int32_t* instance, int32_t* table, int B, int T, int t_in, int H, int W, int id_lo, int id_hi,
+                       void* stream);
+int c2m_instance_compact(const int32_t* table, int32_t* ids, int32_t* boxes, int32_t* count, int32_t* overflow, int B,
+                         int t_in, int nid, int id_lo, int min_pixels, int max_nodes, void* stream);
+
 /* ---- measurement (events.hip): timing events without the system-scope fence of a default hipEventRecord; used by the
  * roofline measurement of bench.py (HIP events on the launch stream), never by the product path.        */
 int c2m_event_create(void** event_out);
