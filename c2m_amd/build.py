@@ -19,7 +19,8 @@ ARCH = "gfx950"
 NOSLP = ["-fno-slp-vectorize"]
 SOURCES = {"conv_igemm.hip": NOSLP, "conv_nc8.hip": NOSLP, "conv_wino.hip": NOSLP, "conv_wino4.hip": NOSLP, "conv_ring.hip": NOSLP, "norm.hip": NOSLP, "losses.hip": NOSLP,
            "optim.hip": ["-ffp-contract=off"] + NOSLP, "data_prep.hip": ["-ffp-contract=off"] + NOSLP,
-           "warp.hip": ["-ffp-contract=off"] + NOSLP, "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],
+           "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
+           "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],
            "flownet_ops.hip": ["-ffp-contract=off"] + NOSLP, "gnn.hip": ["-ffp-contract=off"] + NOSLP}
 
 
@@ -35,7 +36,7 @@ def build(force=False, verbose=False, variant=None, defines=()):
     the environment variable C2M_AMD_LIB; the default build takes neither."""
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    common = [os.path.join(CSRC, h) for h in ("common.h", "dtype.h", "conv_store.h")] + \
+    common = [os.path.join(CSRC, h) for h in ("common.h", "dtype.h", "conv_store.h", "warp_coord.h")] + \
         [os.path.join(os.path.dirname(HERE), "include", "c2m_geom.h")]
     suffix = f"_{variant}" if variant else ""
     lib = LIB.replace(".so", suffix + ".so")

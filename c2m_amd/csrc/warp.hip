@@ -14,41 +14,7 @@
 // row segments; coordinates/weights are computed once per pixel and reused across a chunk of channels.
 #include "common.h"
 #include "dtype.h"
-
-__device__ __forceinline__ float lin_m1_1(int i, int steps) {
-    if (steps <= 1) return -1.0f;
-    const float step = 2.0f / (float)(steps - 1);
-    const int half = steps / 2;
-    return i < half ? fmaf(step, (float)i, -1.0f) : fmaf(-step, (float)(steps - 1 - i), 1.0f);
-}
-
-struct WarpCoord {
-    int x0, y0, x1, y1;
-    float nw, ne, sw, se;   // weights of (y0,x0) (y0,x1) (y1,x0) (y1,x1)
-    float w_, e_, n_, s_;
-    bool okx1, oky1;
-    float gmx, gmy;         // d(ix)/d(flow_x), d(iy)/d(flow_y) incl. the border-clip gate
-};
-
-__device__ __forceinline__ WarpCoord warp_coord(float fx, float fy, int x, int y, int H, int W) {
-    WarpCoord c;
-    const float cx = (float)(((double)W - 1.0) / 2.0), cy = (float)(((double)H - 1.0) / 2.0);
-    const float gx = lin_m1_1(x, W) + fx / cx;
-    const float gy = lin_m1_1(y, H) + fy / cy;
-    float ix = fmaf(gx + 1.0f, (float)W / 2.0f, -0.5f);
-    float iy = fmaf(gy + 1.0f, (float)H / 2.0f, -0.5f);
-    // clip_coordinates_set_grad (ATen GridSampler.h): gradient gate is 0 on/outside the border
-    c.gmx = (ix > 0.0f && ix < (float)(W - 1)) ? ((float)W / 2.0f) / cx : 0.0f;
-    c.gmy = (iy > 0.0f && iy < (float)(H - 1)) ? ((float)H / 2.0f) / cy : 0.0f;
-    ix = fminf((float)(W - 1), fmaxf(ix, 0.0f));
-    iy = fminf((float)(H - 1), fmaxf(iy, 0.0f));
-    const float xw = floorf(ix), yn = floorf(iy);
-    c.w_ = ix - xw; c.e_ = 1.0f - c.w_; c.n_ = iy - yn; c.s_ = 1.0f - c.n_;
-    c.nw = c.s_ * c.e_; c.ne = c.s_ * c.w_; c.sw = c.n_ * c.e_; c.se = c.n_ * c.w_;
-    c.x0 = (int)xw; c.y0 = (int)yn; c.x1 = c.x0 + 1; c.y1 = c.y0 + 1;
-    c.okx1 = c.x1 < W; c.oky1 = c.y1 < H;
-    return c;
-}
+#include "warp_coord.h"
 
 // grid: x = pixel blocks over N*H*W, y = channel chunk
 template <class T>

@@ -2541,6 +2541,75 @@ def occlusion_splat(flow, want_map=True, want_clip=False):
     return occ, clip
 
 
+def _label_warp_plan(flow, planes_f, planes_i, occ, threshold):
+    """Shapes and dtypes of label_warp, checked before anything is launched: (B, T, H, W, Cf, Ci)."""
+    if flow.dim() not in (4, 5) or flow.shape[1] != 2:
+        raise ValueError(f"flow must be [B,2,T,H,W] or [B,2,H,W], got {tuple(flow.shape)}")
+    if flow.dtype != torch.float32:
+        raise ValueError(f"flow must be fp32 (coordinates are never rounded), got {flow.dtype}")
+    B, (H, W) = flow.shape[0], flow.shape[-2:]
+    T = flow.shape[2] if flow.dim() == 5 else 1
+    if planes_f is None and planes_i is None:
+        raise ValueError("label_warp needs planes_f or planes_i")
+    chans = []
+    for name, t, dtype in (("planes_f", planes_f, torch.float32), ("planes_i", planes_i, torch.int32)):
+        if t is None:
+            chans.append(0)
+            continue
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+        if t.dim() != 4 or t.shape[0] != B or tuple(t.shape[-2:]) != (H, W):
+            raise ValueError(f"{name} must be [{B},C,{H},{W}] for flow {tuple(flow.shape)}, got {tuple(t.shape)}")
+        chans.append(t.shape[1])
+    if occ is not None:
+        if threshold is None:
+            raise ValueError("occ needs a threshold")
+        if occ.dtype != torch.float32:
+            raise ValueError(f"occ must be fp32, got {occ.dtype}")
+        want = (B, 1, T, H, W) if flow.dim() == 5 else (B, 1, H, W)
+        if tuple(occ.shape) != want:
+            raise ValueError(f"occ must be {want} for flow {tuple(flow.shape)}, got {tuple(occ.shape)}")
+    elif threshold is not None:
+        raise ValueError("a threshold needs occ")
+    return B, T, H, W, chans[0], chans[1]
+
+
+def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fill_id=0):
+    """Label maps of one frame carried along a backward flow, nearest neighbour: out[b, c, t, y, x] = planes[b, c, sy, sx] with
+    (sx, sy) the pixel nearest (ties to even) to the position flow_warp reads for (x, y) under flow[b, :, t] -- the same
+    coordinates, after the border clamp (csrc/warp_coord.h).  Nothing is blended: ids stay ids, one-hot stays one-hot.
+
+    flow [B,2,T,H,W] fp32 in pixels (a view with dense rows is read in place) or [B,2,H,W] (T = 1); planes_f [B,Cf,H,W] fp32,
+    planes_i [B,Ci,H,W] int32, either may be None or have 0 channels.  occ [B,1,T,H,W] (or [B,1,H,W]) with `threshold`: where
+    occ < threshold the INTEGER outputs are `fill_id`; float planes are not touched.
+    Returns (out_f [B,Cf,T,H,W] fp32 or None, out_i [B,Ci,T,H,W] int32 or None).  One launch, no atomics, no autograd."""
+    for t in (flow, planes_f, planes_i, occ):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    B, T, H, W, Cf, Ci = _label_warp_plan(flow, planes_f, planes_i, occ, threshold)
+    if not -2 ** 31 <= int(fill_id) < 2 ** 31:
+        raise ValueError(f"fill_id must be an int32 value, got {fill_id}")
+    for t in (flow, planes_f, planes_i, occ):
+        if t is not None and t.device.index != _cur_device():
+            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    flow = flow.detach()
+    if flow.stride(-1) != 1 or flow.stride(-2) != W:
+        flow = flow.contiguous()
+    sb, sc = flow.stride(0), flow.stride(1)
+    st = flow.stride(2) if flow.dim() == 5 else 0
+    dev = flow.device
+    out_f = None if planes_f is None else torch.empty(B, Cf, T, H, W, device=dev, dtype=torch.float32)
+    out_i = None if planes_i is None else torch.empty(B, Ci, T, H, W, device=dev, dtype=torch.int32)
+    pf = _f(planes_f.detach()) if Cf else None
+    pi = _f(planes_i) if Ci else None
+    occ = None if occ is None else _f(occ.detach())
+    if B * T * H * W and Cf + Ci:
+        _lib.check(_lib.lib().c2m_label_warp(_p(flow), sb, sc, st, _p(occ), float(threshold or 0.0), int(fill_id), _p(pf), Cf,
+                                             _p(pi), Ci, B, T, H, W, _p(out_f) if Cf else None, _p(out_i) if Ci else None,
+                                             _stream()), "label_warp")
+    return out_f, out_i
+
+
 # =============================================================================================== losses
 class _L1MeanFn(torch.autograd.Function):
     @staticmethod

@@ -331,6 +331,20 @@ long c2m_occlusion_splat_workspace_bytes(long nimg, int H, int W);
 int c2m_occlusion_splat(const float* flow, long sb, long sc, long st, int B, int T, int H, int W, float* occ,
                         float* clip, void* workspace, void* stream);
 
+/* ---- label propagation along the generator's flow (label_warp.hip): rollouts of c2m_amd.interactive -----------------------
+ * The reference has no counterpart: it gets the label maps of a frame from Panoptic-DeepLab and an offline tracker.  Frame t of
+ * `generated` takes pixel p from position s(p) of the last input frame (utils/ops.py:183-202 resample(); c2m_flow_warp_fwd), so
+ * the label of p in frame t is the label of the pixel nearest to s(p): a nearest-neighbour gather with the bilinear warp's own
+ * coordinates (csrc/warp_coord.h, after the border clamp), rounded half to even as ATen's nearest grid_sample does.
+ * flow [B][2][T][H][W] fp32 in pixels, element strides sb / sc / st of sample / channel / frame, rows dense (a [B][2][H][W]
+ * flow: T = 1, st = 0); planes_f [B][Cf][H][W] fp32 -> out_f [B][Cf][T][H][W], planes_i [B][Ci][H][W] int32 -> out_i
+ * [B][Ci][T][H][W]; words are copied, never blended.  Cf or Ci may be 0 (its pointers are then not read).  occ [B][1][T][H][W]
+ * fp32 or NULL: where occ < threshold the INTEGER outputs get fill_id (a disoccluded pixel belongs to no known object); float
+ * planes are not touched.  One launch, no atomics, no workspace; 64-bit indexing when a tensor has >= 2^31 elements.        */
+int c2m_label_warp(const float* flow, long sb, long sc, long st, const float* occ, float threshold, int fill_id,
+                   const float* planes_f, int Cf, const int32_t* planes_i, int Ci, int B, int T, int H, int W, float* out_f,
+                   int32_t* out_i, void* stream);
+
 /* ---- loss reductions (losses.hip) ---------------------------------------------------------------------------
  * losses/losses.py:180-189 L1MaskedLoss (also :60-65 VGG L1, model.py:118-121 feature matching); :152-177 SSIM. */
 int c2m_l1_mean_fwd(const void* a, const void* b, const float* mask, float* out, long total, int C, long inner,
