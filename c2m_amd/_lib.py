@@ -102,6 +102,12 @@ _SIGS = {
     "c2m_occlusion_splat": (c_int, [c_void_p, c_long, c_long, c_long] + [c_int] * 4 + [c_void_p] * 4),
     "c2m_label_warp": (c_int, [c_void_p, c_long, c_long, c_long, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 +
                        [c_void_p] * 3),
+    "c2m_render_frames": (c_int, [c_void_p, c_int] + [c_int] * 8 + [c_void_p, c_void_p]),
+    "c2m_render_flow_workspace_bytes": (c_long, [c_int]),
+    "c2m_render_flow": (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_void_p]),
+    "c2m_render_instances": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "c2m_draw_overlays_max_boxes": (c_int, []),
+    "c2m_draw_overlays": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "c2m_l1_mean_fwd": (c_int, [c_void_p] * 4 + [c_long, c_int, c_long, c_void_p, c_int, c_void_p]),
     "c2m_relu_tap_bwd": (c_int, [c_void_p] * 5 + [c_long, c_int, c_void_p]),
     "c2m_l1_mean_bwd": (c_int, [c_void_p] * 6 + [c_long, c_int, c_long, c_int, c_void_p]),

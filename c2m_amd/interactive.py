@@ -431,7 +431,8 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
       generated [B,3,K*T,H,W]; bg_mask [B,11,K*T,H,W], fg_mask [B,9,K*T,H,W], instance_mask [B,1,K*T,H,W]: the
       propagated maps of every predicted frame; outputs: the K dicts of model.inference;
       ids [K][B, N]: the objects each segment started with (ops.instance_boxes); boxes [K][B, N, T, 4], presence
-      [K][B, N, T]: predicted_boxes of them in the segment's frames; drag_errors [K]: drag_error of the segment's drags.
+      [K][B, N, T]: predicted_boxes of them in the segment's frames; targets [K]: drag_targets of the segment's drags;
+      drag_errors [K]: drag_error of them.
     A sample whose every object has left the frame (or is covered) ends the rollout with the "no object" ValueError of
     graph_from_boxes, prefixed with the segment.  Per segment the host reads what click_to_move reads plus the
     [B, N, T, 5] box table; frames and maps stay on the device."""
@@ -447,7 +448,7 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
     id_range = box_kw.get("id_range", (1000, 19000))
     inputs = dict(video=video, bg_mask=bg_mask, fg_mask=fg_mask, instance_mask=instance_mask, input_of=input_of,
                   input_occ=input_occ)
-    res = dict(outputs=[], maps=[], ids=[], boxes=[], presence=[], drag_errors=[])
+    res = dict(outputs=[], maps=[], ids=[], boxes=[], presence=[], targets=[], drag_errors=[])
     out = maps = None
     for k, drags in enumerate(segments):
         try:
@@ -466,7 +467,8 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
         res["ids"].append(ids)
         res["boxes"].append(boxes)
         res["presence"].append(presence)
-        res["drag_errors"].append(drag_error(drag_targets(drags, info["nodes"], info["edges"], t_in, T), boxes, presence))
+        res["targets"].append(drag_targets(drags, info["nodes"], info["edges"], t_in, T))
+        res["drag_errors"].append(drag_error(res["targets"][-1], boxes, presence))
     maps = res.pop("maps")
     res["generated"] = torch.cat([o["generated"] for o in res["outputs"]], 2)
     for key in ("bg_mask", "fg_mask", "instance_mask"):

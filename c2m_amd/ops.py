@@ -2610,6 +2610,171 @@ def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fil
     return out_f, out_i
 
 
+# =============================================================================================== rendering (csrc/render.hip)
+def _sheet_plan(name, x, channels, size, dtypes=(torch.float32, torch.bfloat16)):
+    """Checks of one [B,C,T,H,W] device tensor that becomes a sheet -> (B, C, T, H, W, rows, cols)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
+    if x.dim() != 5 or x.shape[1] not in channels:
+        raise ValueError(f"{name} must be [B, C, T, H, W] with C in {tuple(channels)}, got {tuple(x.shape)}")
+    rows, cols = (int(v) for v in size)
+    if rows < 1 or cols < 1 or x.shape[0] > rows * cols:
+        raise ValueError(f"{name}: B = {x.shape[0]} samples do not fit size = {rows} x {cols} cells")
+    if not x.is_cuda:                   # after the shape checks: those are the same with or without a device
+        raise RuntimeError(f"{name}: c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if x.device.index != _cur_device():
+        raise RuntimeError(f"{name}: tensor on cuda:{x.device.index} but the current device is cuda:{_cur_device()}")
+    B, C, T, H, W = x.shape
+    return B, C, T, H, W, rows, cols
+
+
+def render_frames(x, size, normalize=False):
+    """Frames or one-channel maps [B,C,T,H,W] (C in {1, 3}, fp32 or bf16) -> uint8 sheet [T, rows*H, cols*W, C]; sample b in
+    cell (b // cols, b % cols) of size = (rows, cols), the other cells zero.  Level = trunc(clip(x * 255, 0, 255)), with
+    normalize (x + 1) / 2 * 255: the reference's tensor2im / tensor2occ bit for bit; NaN -> 0.  One launch."""
+    B, C, T, H, W, rows, cols = _sheet_plan("x", x, (1, 3), size)
+    with torch.no_grad():
+        x = _f(x.detach())
+        out = torch.empty(T, rows * H, cols * W, C, device=x.device, dtype=torch.uint8)
+        if out.numel():
+            _lib.check(_lib.lib().c2m_render_frames(_p(x), _dt(x), B, C, T, H, W, rows, cols, int(bool(normalize)), _p(out),
+                                                    _stream()), "render_frames")
+    return out
+
+
+def render_flow(flow, size, scale=None):
+    """Flow [B,2,T,H,W] in pixels -> uint8 RGB sheet [T, rows*H, cols*W, 3] in the Middlebury colour code.  scale None: every
+    frame's sheet is normalised by its largest radius over ALL samples (the reference's tensor2flow; |component| > 1e7 is
+    unknown = black, an all-zero sheet is black); scale s: u * s, v * s without normalisation (compute_flow_color_map, s = 3).
+    Empty cells hold zero flow (near-white / white).  NaN components -> black."""
+    B, _, T, H, W, rows, cols = _sheet_plan("flow", flow, (2,), size)
+    with torch.no_grad():
+        flow = _f(flow.detach())
+        out = torch.empty(T, rows * H, cols * W, 3, device=flow.device, dtype=torch.uint8)
+        if out.numel():
+            L = _lib.lib()
+            ws = None if scale is not None else torch.empty(max(L.c2m_render_flow_workspace_bytes(T) // 8, 1), device=flow.device,
+                                                            dtype=torch.int64)
+            _lib.check(L.c2m_render_flow(_p(flow), _dt(flow), B, T, H, W, rows, cols, 0 if scale is None else 1,
+                                         float(scale or 0.0), _p(out), _p(ws), _stream()), "render_flow")
+    return out
+
+
+def _u8_table(name, t, device, last=3):
+    t = torch.as_tensor(t)
+    if t.dtype != torch.uint8 or t.dim() < 1 or t.shape[-1] != last:
+        raise ValueError(f"{name} must be uint8 [..., {last}], got {t.dtype} {tuple(t.shape)}")
+    return _f(t.to(device))
+
+
+def render_instances(ids, size, palette, base=None, id_range=(1000, 19000), alpha=128):
+    """Instance ids [B,1,T,H,W] int32 -> uint8 RGB sheet: pixels with lo <= id < hi tinted with palette[id % P]
+    ((c * (256 - alpha) + p * alpha) >> 8), instance borders (id differs from a 4-neighbour inside the frame, the reference's
+    get_edges) in the solid palette colour of the larger id.  base: an RGB sheet to draw onto (not modified), None = black."""
+    B, _, T, H, W, rows, cols = _sheet_plan("ids", ids, (1,), size, dtypes=(torch.int32,))
+    lo, hi = (int(v) for v in id_range)
+    if lo < 0 or hi < lo:
+        raise ValueError(f"id_range must be 0 <= lo <= hi, got {id_range}")
+    if not 0 <= int(alpha) <= 256:
+        raise ValueError(f"alpha must be in 0..256, got {alpha}")
+    palette = _u8_table("palette", palette, ids.device)
+    if palette.dim() != 2 or palette.shape[0] < 1:
+        raise ValueError(f"palette must be uint8 [P, 3] with P >= 1, got {tuple(palette.shape)}")
+    shape = (T, rows * H, cols * W, 3)
+    if base is not None:
+        if not base.is_cuda or base.dtype != torch.uint8 or tuple(base.shape) != shape:
+            raise ValueError(f"base must be a uint8 HIP tensor of shape {shape}, got {base.dtype} {tuple(base.shape)} on {base.device}")
+        base = _f(base)
+    with torch.no_grad():
+        ids = _f(ids)
+        out = torch.empty(shape, device=ids.device, dtype=torch.uint8)
+        if out.numel():
+            _lib.check(_lib.lib().c2m_render_instances(_p(ids), B, T, H, W, rows, cols, _p(base), _p(palette), palette.shape[0], lo,
+                                                       hi, int(alpha), _p(out), _stream()), "render_instances")
+    return out
+
+
+def draw_overlays(sheet, size, boxes=None, presence=None, box_colors=None, points=None, point_sample=None, point_count=None,
+                  line_colors=None):
+    """Draws box outlines and drag paths onto an RGB sheet [T, rows*H, cols*W, 3] uint8 IN PLACE and returns it.
+
+    boxes [B,N,T,4] int32 pixel edges (x0, y0, x1, y1) in cell coordinates and presence [B,N,T] bool (what
+    interactive.predicted_boxes returns; CPU tensors are copied over): the 1-pixel outline of [x0, x1-1] x [y0, y1-1] of every
+    present box, colour box_colors [B,N,3] uint8; N <= 64.  points [D,P,2] int32 (x, y), point_sample [D] (the sample a path
+    belongs to), point_count [D,T] (frame t shows the first point_count[d, t] points and a 3x3 marker on the last of them),
+    line_colors [D,3] uint8.  Per pixel the last covering primitive wins: boxes in node order, then paths in order; nothing is
+    drawn outside a sample's own cell."""
+    if not isinstance(sheet, torch.Tensor) or not sheet.is_cuda:
+        raise RuntimeError("sheet: c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if sheet.device.index != _cur_device():
+        raise RuntimeError(f"sheet: tensor on cuda:{sheet.device.index} but the current device is cuda:{_cur_device()}")
+    if sheet.dtype != torch.uint8 or sheet.dim() != 4 or sheet.shape[-1] != 3 or not sheet.is_contiguous():
+        raise ValueError(f"sheet must be a contiguous uint8 [T, rows*H, cols*W, 3] tensor, got {sheet.dtype} {tuple(sheet.shape)}")
+    rows, cols = (int(v) for v in size)
+    T = sheet.shape[0]
+    if rows < 1 or cols < 1 or sheet.shape[1] % rows or sheet.shape[2] % cols:
+        raise ValueError(f"size = {rows} x {cols} does not divide the sheet {tuple(sheet.shape)}")
+    H, W = sheet.shape[1] // rows, sheet.shape[2] // cols
+    dev = sheet.device
+    as_i32 = lambda t: _f(torch.as_tensor(t).to(device=dev, dtype=torch.int32))
+    B = N = D = P = 0
+    if boxes is not None:
+        boxes = torch.as_tensor(boxes)
+        if boxes.dim() != 4 or boxes.shape[2] != T or boxes.shape[3] != 4 or boxes.dtype.is_floating_point:
+            raise ValueError(f"boxes must be integer [B, N, {T}, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+        B, N = boxes.shape[:2]
+        if N > _lib.lib().c2m_draw_overlays_max_boxes():
+            raise ValueError(f"boxes: N = {N} nodes per sample, the overlay kernel keeps at most "
+                             f"{_lib.lib().c2m_draw_overlays_max_boxes()} (the cap of ops.instance_boxes)")
+        presence = torch.ones(B, N, T, dtype=torch.bool) if presence is None else torch.as_tensor(presence)
+        if tuple(presence.shape) != (B, N, T):
+            raise ValueError(f"presence must be [B, N, T] = {(B, N, T)}, got {tuple(presence.shape)}")
+        presence = _f((presence != 0).to(device=dev, dtype=torch.uint8))
+        if box_colors is None:
+            raise ValueError("box_colors [B, N, 3] uint8 is needed with boxes")
+        box_colors = _u8_table("box_colors", box_colors, dev)
+        if tuple(box_colors.shape) != (B, N, 3):
+            raise ValueError(f"box_colors must be uint8 [B, N, 3] = {(B, N, 3)}, got {tuple(box_colors.shape)}")
+        boxes = as_i32(boxes)
+    if points is not None:
+        points = torch.as_tensor(points)
+        if points.dim() != 3 or points.shape[2] != 2 or points.dtype.is_floating_point:
+            raise ValueError(f"points must be integer [D, P, 2], got {points.dtype} {tuple(points.shape)}")
+        D, P = points.shape[:2]
+        if point_sample is None or point_count is None or line_colors is None:
+            raise ValueError("point_sample [D], point_count [D, T] and line_colors [D, 3] are needed with points")
+        point_sample, point_count = torch.as_tensor(point_sample), torch.as_tensor(point_count)
+        if tuple(point_sample.shape) != (D,) or tuple(point_count.shape) != (D, T):
+            raise ValueError(f"point_sample must be [{D}] and point_count [{D}, {T}], got {tuple(point_sample.shape)} and "
+                             f"{tuple(point_count.shape)}")
+        line_colors = _u8_table("line_colors", line_colors, dev)
+        if tuple(line_colors.shape) != (D, 3):
+            raise ValueError(f"line_colors must be uint8 [D, 3] = {(D, 3)}, got {tuple(line_colors.shape)}")
+        if D and (int(point_sample.min()) < 0 or int(point_sample.max()) >= rows * cols):
+            raise ValueError(f"point_sample holds a sample outside the {rows} x {cols} cells")
+        B = max(B, int(point_sample.max()) + 1) if D else B
+        points, point_sample, point_count = as_i32(points), as_i32(point_sample), as_i32(point_count)
+    if B > rows * cols:
+        raise ValueError(f"boxes: B = {B} samples do not fit size = {rows} x {cols} cells")
+    if B * T >= 65536:
+        raise ValueError(f"sheet: B * T = {B * T} cells, the overlay launch takes fewer than 65536")
+    if boxes is not None and boxes.shape[0] < B:            # paths of samples past the boxes' batch: pad with absent boxes
+        pad = B - boxes.shape[0]
+        boxes = torch.cat([boxes, boxes.new_zeros(pad, N, T, 4)])
+        presence = torch.cat([presence, presence.new_zeros(pad, N, T)])
+        box_colors = torch.cat([box_colors, box_colors.new_zeros(pad, N, 3)])
+    if sheet.numel() and B and (N or D * P):
+        with torch.no_grad():
+            _lib.check(_lib.lib().c2m_draw_overlays(_p(sheet), B, T, H, W, rows, cols, _p(boxes) if N else None,
+                                                    _p(presence) if N else None, _p(box_colors) if N else None, N,
+                                                    _p(points) if D * P else None, _p(point_sample) if D * P else None,
+                                                    _p(point_count) if D * P else None, _p(line_colors) if D * P else None,
+                                                    D if P else 0, P, _stream()), "draw_overlays")
+    return sheet
+
+
 # =============================================================================================== losses
 class _L1MeanFn(torch.autograd.Function):
     @staticmethod

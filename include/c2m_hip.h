@@ -395,6 +395,48 @@ int c2m_instance_stats(const int32_t* instance, int32_t* table, int B, int T, in
 int c2m_instance_compact(const int32_t* table, int32_t* ids, int32_t* boxes, int32_t* count, int32_t* overflow, int B,
                          int t_in, int nid, int id_lo, int min_pixels, int max_nodes, void* stream);
 
+/* ---- rendering (render.hip): results as uint8 pictures on the device ------------------------------------------------
+ * A SHEET is uint8 [T][rows*H][cols*W][C] (HWC); sample b sits in cell (b / cols, b % cols), as the reference's merge
+ * (utils/utils.py:26-43) lays samples out; cells without a sample hold zero input.  B <= rows * cols.  Inputs are dense
+ * [B][C][T][H][W]; dt = 0 fp32, 1 bf16 (csrc/dtype.h; bf16 is widened to fp32 first, as the reference's .float()).
+ * Number formats are numpy's in the reference, operation by operation (see render.hip).  No allocation, no float atomics.
+ *
+ * c2m_render_frames: utils/utils.py:46-72 (tensor2im, tensor2occ; evaluator/evaluator.py:185-254).  C in {1, 3};
+ *   level = trunc(clip(x * 255, 0, 255)), or (x + 1) / 2 * 255 with normalize, in fp32 like numpy.  NaN -> 0 (numpy leaves the
+ *   uint8 conversion of NaN undefined).
+ * c2m_render_flow: the Middlebury colour code, RGB sheet.  mode 0 = sheet-normalised (utils/utils.py:75-80 tensor2flow ->
+ *   utils/ops.py:143-175 compute_flow_img / flow2img): components with |u| or |v| > 1e7 are unknown (zero for the radius,
+ *   black in the picture), maxrad = the largest radius over the whole sheet of frame t (a NaN radius makes it -1, Python's
+ *   max(-1, nan)), u / maxrad + eps, v / maxrad + eps, all in double; an all-zero sheet is 0 / 0 = NaN = black.  workspace:
+ *   c2m_render_flow_workspace_bytes(T) bytes, 8-byte aligned (zeroed by the call; integer max of the radius' bit pattern).
+ *   mode 1 = fixed scale (utils/utils.py:287-305 save_flows -> utils/ops.py:84-140 compute_flow_color_map): u * scale,
+ *   v * scale (the reference: 3), no normalisation, in double (numpy keeps float32 up to the wheel position there, with an
+ *   arctan2 that is not correctly rounded: 2e-5 of a normal flow's pixels differ by one level); workspace may be NULL.
+ *   NaN components -> 0 in both modes.
+ * c2m_render_instances: ids [B][1][T][H][W] int32 -> RGB sheet on top of `base` (an RGB sheet, NULL = black; may be `out`).
+ *   A pixel whose id differs from a 4-neighbour inside its frame (utils/ops.py:278-284 get_edges) and whose largest id m among
+ *   itself and those neighbours is in [id_lo, id_hi) gets palette[m % P]; otherwise a pixel whose id is in the range is
+ *   tinted (base * (256 - alpha) + palette[id % P] * alpha) >> 8, alpha in 0..256; other pixels keep base.  id_lo >= 0.
+ * c2m_draw_overlays: draws onto an RGB sheet in place (utils/utils.py:244-284 draw_bbox / save_images_w_bbox).  Gather form:
+ *   every pixel of a cell walks the cell's primitives in order -- boxes by node, then polylines by index -- and keeps the
+ *   last that covers it, so nothing is drawn outside the cell.  boxes [B][N][T][4] int32 pixel edges (x0, y0, x1, y1) in
+ *   cell coordinates: the 1-pixel outline of [x0, x1-1] x [y0, y1-1] where presence [B][N][T] (bytes) is non-zero, colour
+ *   box_rgb [B][N][3]; N <= c2m_draw_overlays_max_boxes() (64, the table kept in LDS).  Polyline d of sample sample[d]:
+ *   points [D][P][2] int32 (x, y); frame t shows the first min(count[d][t], P) points and a 3x3 marker on the last shown one,
+ *   colour line_rgb [D][3].  A segment a -> b with n = max(|dx|, |dy|) covers, for i = 0..n along the major axis (x when
+ *   |dx| >= |dy|), the minor coordinate a_minor + floor((2 * i * d_minor + n) / (2 * n)); n = 0: the single point.      */
+int c2m_render_frames(const void* x, int dt, int B, int C, int T, int H, int W, int rows, int cols, int normalize,
+                      uint8_t* out, void* stream);
+long c2m_render_flow_workspace_bytes(int T);
+int c2m_render_flow(const void* flow, int dt, int B, int T, int H, int W, int rows, int cols, int mode, float scale,
+                    uint8_t* out, void* workspace, void* stream);
+int c2m_render_instances(const int32_t* ids, int B, int T, int H, int W, int rows, int cols, const uint8_t* base,
+                         const uint8_t* palette, int P, int id_lo, int id_hi, int alpha, uint8_t* out, void* stream);
+int c2m_draw_overlays_max_boxes(void);
+int c2m_draw_overlays(uint8_t* sheet, int B, int T, int H, int W, int rows, int cols, const int32_t* boxes,
+                      const uint8_t* presence, const uint8_t* box_rgb, int N, const int32_t* points, const int32_t* sample,
+                      const int32_t* count, const uint8_t* line_rgb, int D, int P, void* stream);
+
 /* ---- measurement (events.hip): timing events without the system-scope fence of a default hipEventRecord; used by the
  * roofline measurement of bench.py (HIP events on the launch stream), never by the product path.        */
 int c2m_event_create(void** event_out);
