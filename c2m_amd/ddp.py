@@ -167,6 +167,7 @@ class GradientReducer:
             if s is not None:
                 with torch.cuda.stream(s):
                     b.views[i].copy_(p.grad)
+                ops.deferred_grad_done(p.grad)    # dropped below: its address must not stay registered as made on that stream
             else:
                 b.views[i].copy_(p.grad)
             p.grad = b.views[i]
@@ -189,6 +190,8 @@ class GradientReducer:
             if b.pending == 0:
                 b.ready = True
                 self._launch_ready()
+
+    _on_grad._c2m_asks_grad_stream = True     # (ops._may_defer: this hook takes its copy stream from ops.deferred_grad_stream)
 
     def _launch_ready(self):
         while self.next_slot < len(self.order) and self.buckets[self.order[self.next_slot]].ready:

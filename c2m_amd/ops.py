@@ -268,21 +268,27 @@ class aux_branch:
 
 # ---- deferred weight gradients (round 5): see _ConvFn.backward
 _DEFER_WGRAD = os.environ.get("C2M_DEFER_WGRAD", "1") != "0"
-_defer = {"on": False, "devs": set(), "seen": set(), "hold": collections.deque(), "grads": {}, "by_w": {}}
+_defer = {"on": False, "params": {}, "devs": set(), "seen": set(), "hold": collections.deque(), "grads": {}, "by_p": {}}
 
 
 class deferred_wgrads:
-    """`with ops.deferred_wgrads(): loss.backward()` -- weight gradients of the convolutions are computed on the side stream and
-    joined once, when the block exits (on the stream that is current then).  Parameter gradients must not be read inside the block."""
+    """`with ops.deferred_wgrads(params=conv_weights_and_biases): loss.backward()` -- the weight / bias gradients of the
+    convolutions whose parameters are listed are computed on the side stream and joined once, when the block exits (on the stream
+    that is current then, also when the body raises).  Listing a parameter is a promise: inside this backward its gradient is
+    produced by ops.conv nodes only (no other op of the graph reads the parameter) and nobody reads it before the block exits.
+    Everything the node can check for itself it does (_may_defer); a convolution whose parameters are not listed, and every case
+    the checks turn down, computes its gradients on the backward's own stream as without the block."""
 
-    def __init__(self, enabled=True):
-        self.enabled = bool(enabled) and _DEFER_WGRAD
+    def __init__(self, enabled=True, params=None):
+        self.params = {id(p): p for p in (params or ())}
+        self.enabled = bool(enabled) and _DEFER_WGRAD and bool(self.params)
 
     def __enter__(self):
         _defer["on"] = self.enabled
+        _defer["params"] = self.params if self.enabled else {}
         _defer["seen"].clear()
         _defer["grads"].clear()
-        _defer["by_w"].clear()
+        _defer["by_p"].clear()
         return self
 
     def __exit__(self, *exc):
@@ -293,13 +299,35 @@ class deferred_wgrads:
         _defer["devs"].clear()
         _defer["hold"].clear()            # (the joined stream orders every later write behind the side stream's reads)
         _defer["grads"].clear()
+        _defer["by_p"].clear()
+        _defer["seen"].clear()
+        _defer["params"] = {}
         return False
 
 
 def deferred_grad_stream(grad):
     """The side stream if `grad` is a weight / bias gradient that a deferred launch of the current backward is still producing
-    (ops.deferred_wgrads), else None.  For whoever touches a parameter gradient INSIDE backward (the gradient reducer's hook)."""
+    (ops.deferred_wgrads), else None.  For whoever touches a parameter gradient INSIDE backward (the gradient reducer's hook).
+    A hook that asks this carries `_c2m_asks_grad_stream = True`: parameters with any other hook are not deferred."""
     return _defer["grads"].get(grad.data_ptr()) if _defer["grads"] else None
+
+
+def deferred_grad_done(grad):
+    """`grad` has been consumed on the stream deferred_grad_stream named and is about to be dropped: its address no longer stands
+    for a gradient in flight (the allocator may hand the block to a tensor made on another stream)."""
+    _defer["grads"].pop(grad.data_ptr(), None)
+
+
+def _may_defer(p):
+    """The gradient of parameter `p` may stay unjoined on the side stream until the block exits: the caller listed it, it is a
+    leaf without a gradient (AccumulateGrad adopts the tensor: no kernel), this is its first gradient in this backward (a second
+    one is summed by the engine on the backward's stream) and it carries no hook that would read the gradient inside backward."""
+    if p is None or id(p) not in _defer["params"] or id(p) in _defer["seen"] or not p.is_leaf or p.grad is not None:
+        return False
+    for hooks in (p._backward_hooks, getattr(p, "_post_accumulate_grad_hooks", None)):
+        if hooks and not all(getattr(h, "_c2m_asks_grad_stream", False) for h in hooks.values()):
+            return False
+    return True
 
 
 def _record_stream_all(stream, *objs):
@@ -1586,6 +1614,8 @@ class _ConvFn(torch.autograd.Function):
     def forward(ctx, x, w, b, stride, pad, reflect, act, dgrad_rows=None, slope=LRELU_SLOPE):
         _dev(x, w, b)
         ctx.slope = slope = float(slope)
+        # the caller's weight and bias objects, for backward's deferral checks (weak: the node keeps no parameter alive)
+        ctx.wb_refs = (weakref.ref(w), weakref.ref(b) if b is not None else None)
         x, w = _f(x), _f(w)
         pl = _plan(x, w, stride, pad, reflect, dgrad_rows)
         L = _lib.lib()
@@ -1748,29 +1778,35 @@ class _ConvFn(torch.autograd.Function):
         # replays of configs[3] / configs[2]: 42.7 / 63.9 ms deferred, 42.4 / 63.5 per node, 43.8 / 66.4 deferred without the object
         # branch -- and a capture would have to hold every dY until its end)
         if need_w and _defer["on"] and not torch.cuda.is_current_stream_capturing():
-            # `with ops.deferred_wgrads():` around backward (TrainStep): the weight gradient of a leaf weight that has no gradient
-            # yet goes to the side stream and is NOT joined here -- nothing reads it before the optimizer (AccumulateGrad adopts the
-            # tensor, no kernel) -- so its split reductions and its tail run under the data-gradient chain of the layers below.
-            # The context's exit joins.  A weight that already has a gradient (a second backward) would be summed by a kernel on
-            # this stream: it joins first and takes the ordinary path.  Limit of the scheme: a convolution weight that ALSO feeds a
-            # non-convolution op in the same graph (none in this model) has the two gradients summed without that join -- run such a
-            # model with C2M_DEFER_WGRAD=0.
-            # (a weight applied twice in one graph -- the sparse-feature encoder with use_fw_of -- has its two gradients summed by
-            # the engine before AccumulateGrad runs, on this stream: the second one joins as well)
-            first_use = w.data_ptr() not in _defer["seen"]
-            _defer["seen"].add(w.data_ptr())
-            if first_use and w.is_leaf and w.grad is None and ConvProfiler.active is None and not _on_aux_stream(x.device):
+            # `with ops.deferred_wgrads(params=...):` around backward (TrainStep): the weight / bias gradient of LISTED leaf
+            # parameters that have no gradient yet goes to the side stream and is NOT joined here -- nothing reads it before the
+            # optimizer (AccumulateGrad adopts the tensor, no kernel) -- so its split reductions and its tail run under the
+            # data-gradient chain of the layers below.  The context's exit joins.  The gradients stay unjoined only when nothing on
+            # this stream can touch them before that (_may_defer, asked for the weight AND the bias): a parameter that already has a
+            # gradient (a second backward: AccumulateGrad sums with a kernel on this stream), that is not a leaf, that got a
+            # gradient earlier in this backward (a weight applied twice -- the sparse-feature encoder with use_fw_of --, a bias
+            # shared by two convolutions: the engine sums the two on this stream) or that carries a hook joins first and takes the
+            # ordinary path.  A parameter that ALSO feeds a non-convolution op of the graph cannot be seen from here: that is
+            # what the caller's list vouches for, and an unlisted parameter is never deferred.
+            w0, b0 = (r() if r is not None else None for r in ctx.wb_refs)
+            defer_ok = (not ctx.needs_input_grad[1] or _may_defer(w0)) and \
+                (not (ctx.has_bias and ctx.needs_input_grad[2]) or _may_defer(b0))
+            for p in (w0, b0):
+                if p is not None:
+                    _defer["seen"].add(id(p))
+            if defer_ok and ConvProfiler.active is None and not _on_aux_stream(x.device):
                 main = torch.cuda.current_stream(x.device)
                 dside = _side_stream(x.device)
                 dside.wait_stream(main)
                 _record_stream_all(dside, x, gy, keep, ctx.nc8_keep)    # freed by autograd right after this node; still being read
                 with torch.cuda.stream(dside):
                     gw, gb = _ConvFn._wgrad(ctx, pl, x, w, gy, keep)
-                for t in (gw, gb):
+                for p, t in ((w0, gw), (b0, gb)):
                     if t is not None:
                         t.record_stream(main)
                         _defer["grads"][t.data_ptr()] = dside
-                _defer["by_w"][w.data_ptr()] = [t.data_ptr() for t in (gw, gb) if t is not None]
+                        if p is not None:
+                            _defer["by_p"][id(p)] = t.data_ptr()
                 _defer["devs"].add(x.device.index)
                 # dY may be shared with the identity path of a residual block (AddBackward hands ONE tensor to both branches): the
                 # engine sums the other branch's gradient into it IN PLACE once nobody else holds it -- while the side stream still
@@ -1787,8 +1823,10 @@ class _ConvFn(torch.autograd.Function):
                 return gx, gw, gb, None, None, None, None, None, None
             if x.device.index in _defer["devs"]:
                 torch.cuda.current_stream(x.device).wait_stream(_side_stream(x.device))
-                for ptr in _defer["by_w"].pop(w.data_ptr(), ()):     # its first gradient is summed with this one on THIS stream:
-                    _defer["grads"].pop(ptr, None)                   # no longer "being produced on the side stream"
+                for p in (w0, b0):                      # a first gradient is summed with this one on THIS stream:
+                    ptr = _defer["by_p"].pop(id(p), None) if p is not None else None
+                    if ptr is not None:
+                        _defer["grads"].pop(ptr, None)  # no longer "being produced on the side stream"
         if side is not None:
             main = torch.cuda.current_stream(x.device)
             side.wait_stream(main)

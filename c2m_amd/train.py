@@ -78,8 +78,9 @@ class TrainStep:
         distributed = dist.is_initialized() and dist.get_world_size() > 1 if distributed is None else distributed
         # leaf weights / biases of the convolution modules: their gradients are deferred to the side stream (ops.deferred_wgrads),
         # the reducer adopts them instead of summing them into its buckets on the backward's stream
-        conv_params = [p for m in c2m.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d))
-                       for p in (m._parameters.get("weight"), m._parameters.get("bias")) if p is not None and p.requires_grad]
+        self.conv_params = conv_params = [
+            p for m in c2m.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.Conv3d))
+            for p in (m._parameters.get("weight"), m._parameters.get("bias")) if p is not None and p.requires_grad]
         self.reducer = GradientReducer(list(c2m.parameters()), bucket_mb=bucket_mb, buffers=list(c2m.buffers()),
                                        force_collectives=force_collectives, measure=measure_comm, measure_buckets=measure_comm_buckets,
                                        comm_dtype=comm_dtype, adopt_params=conv_params) if distributed else None
@@ -197,8 +198,9 @@ class TrainStep:
         if self.reducer is not None and not in_capture:
             self.reducer.arm()
         # weight gradients on the side stream, joined once after the backward (ops.deferred_wgrads); with the gradient reducer the
-        # hook moves an adopted gradient into its bucket on that stream, and a bucket's all-reduce waits for every branch stream
-        with ops.deferred_wgrads():
+        # hook moves an adopted gradient into its bucket on that stream, and a bucket's all-reduce waits for every branch stream.
+        # The list vouches that only ops.conv nodes produce these gradients: the loss is built above, from the model's outputs alone
+        with ops.deferred_wgrads(params=self.conv_params):
             total.backward()
         if self.reducer is not None and not in_capture:
             self.reducer.finish()
