@@ -62,6 +62,10 @@ _SIGS = {
     "c2m_prep_flow_occ": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "c2m_instance_stats": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "c2m_instance_compact": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
+    "c2m_instance_link_max_nodes": (c_int, []),
+    "c2m_instance_slots": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "c2m_instance_overlap": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
+    "c2m_instance_match": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "c2m_event_create": (c_int, [c_void_p]),
     "c2m_event_record": (c_int, [c_void_p, c_void_p]),
     "c2m_event_elapsed_ms": (c_int, [c_void_p, c_void_p, c_void_p]),

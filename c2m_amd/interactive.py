@@ -191,7 +191,29 @@ def graph_to(graph, device):
     return GraphBatch(**{k: v.to(device) if torch.is_tensor(v) else v for k, v in graph.__dict__.items()})
 
 
-def _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, input_occ, z_m, box_kw):
+def _tracked_boxes(model, inst, t_in, input_of, track, box_kw):
+    """The (ids, edges, count) of ops.instance_boxes from tracking.track_instances on the input frames: an object may carry
+    a different id in every input frame; `ids` are the ids of the LAST input frame, the ones the model and the drags read.
+    Also returns the input-frame maps with every tracked object relabelled to that id."""
+    from .tracking import track_instances
+    if t_in < 2:
+        raise ValueError("track= links the objects of several input frames: it needs num_input_frames > 1")
+    _check_continuable(model)
+    kw = dict(box_kw, **(track if isinstance(track, dict) else {}))
+    tr = track_instances(inst[:, :, :t_in], t_in, None, input_of, **kw)
+    # the model reads the ids of every input frame as numbers (the encoder's instance channels): an object gets its
+    # last-input-frame id in the earlier frames too, as maps with stable ids would have it
+    relabelled = inst[:, :, :t_in].clone()
+    for b in range(inst.shape[0]):
+        for n in range(int(tr.count[b])):
+            for f in range(t_in - 1):
+                old, new = int(tr.ids[b, n, f]), int(tr.ids[b, n, t_in - 1])
+                if old != new:
+                    relabelled[b, 0, f][inst[b, 0, f] == old] = new
+    return tr.ids[:, :, t_in - 1].contiguous().numpy(), tr.boxes.numpy(), tr.count.numpy(), relabelled
+
+
+def _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, input_occ, z_m, box_kw, track=None):
     """click_to_move plus what it learnt about the objects on the way: (output dict of model.inference, dict(ids, edges,
     count: ops.instance_boxes of the input frames; nodes: [(sample, node)] per drag))."""
     tp = model.train_params
@@ -202,7 +224,10 @@ def _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, inp
                          f"instance maps {tuple(instance_mask.shape[-2:])}")
     device = next(model.parameters()).device
     inst = instance_mask if instance_mask.dim() == 5 else instance_mask.unsqueeze(1)
-    ids, edges, count = (t.numpy() for t in ops.instance_boxes(inst, t_in, **box_kw))
+    if track:
+        ids, edges, count, inst = _tracked_boxes(model, inst, t_in, input_of, track, box_kw)
+    else:
+        ids, edges, count = (t.numpy() for t in ops.instance_boxes(inst, t_in, **box_kw))
     drags = list(drags)
     _check_drags(drags, inst.shape[0], size[0], size[1])
     clicked = _click_ids(inst[:, 0], drags, t_in) if drags else []
@@ -218,7 +243,7 @@ def _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, inp
 
 
 def click_to_move(model, video, bg_mask, fg_mask, instance_mask, drags, input_of=None, input_occ=None, z_m=None,
-                  **box_kw):
+                  track=None, **box_kw):
     """Predict the num_predicted_frames future frames from the input frames and `drags`; returns the dict of
     model.inference.
 
@@ -226,8 +251,11 @@ def click_to_move(model, video, bg_mask, fg_mask, instance_mask, drags, input_of
     device, H x W = train_params.input_size; only the first num_input_frames frames are read (T may equal it).
     input_of / input_occ: the input-frame flows when the config uses them.  z_m: [B, fc.in_features] motion code; drawn from
     N(0, 1) with the torch CPU generator when None, as the reference's evaluator does.  The trajectory latent is drawn by
-    inference() itself (seed torch for repeatable runs).  box_kw: id_range, min_pixels, max_nodes (ops.instance_boxes)."""
-    return _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, input_occ, z_m, box_kw)[0]
+    inference() itself (seed torch for repeatable runs).  box_kw: id_range, min_pixels, max_nodes (ops.instance_boxes).
+    track: None (the default) takes an object to be the same id in every input frame; True, or a dict of min_iou /
+    same_class, links the objects of the input frames with tracking.track_instances instead (num_input_frames > 1, maps whose
+    ids change from frame to frame; input_of, when given, carries the association; scale_factor != 1 is refused)."""
+    return _predict(model, video, bg_mask, fg_mask, instance_mask, drags, input_of, input_occ, z_m, box_kw, track)[0]
 
 
 # ------------------------------------------------------------------------------------------------ continuing a prediction

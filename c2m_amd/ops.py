@@ -2557,6 +2557,125 @@ def instance_boxes(instance, num_input_frames, id_range=(1000, 19000), min_pixel
     return ids, boxes, count
 
 
+# ---- linking the objects of two instance maps (csrc/instance_link.hip; c2m_amd.tracking is the public interface) ------------
+def _link_nodes(max_nodes, min_pixels=1):
+    max_nodes, min_pixels = int(max_nodes), int(min_pixels)
+    if min_pixels < 1 or max_nodes < 1:
+        raise ValueError("min_pixels and max_nodes must be >= 1")
+    cap = _lib.lib().c2m_instance_link_max_nodes()
+    if max_nodes > cap:
+        raise ValueError(f"max_nodes={max_nodes} is above the kernel cap of {cap} (one wave holds a plane's objects)")
+    return max_nodes, min_pixels
+
+
+def _link_i32(name, t, shape):
+    """An int32 device tensor of exactly `shape` on the current device, contiguous."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    if t.device.index != _cur_device():
+        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    return _f(t)
+
+
+def instance_slots(table, id_range=(1000, 19000), min_pixels=1, max_nodes=64):
+    """Per plane of an instance_stats table [..., id_hi - id_lo, 5], the ids with count >= min_pixels in ascending order; an
+    id's position in that list is its slot.  Unlike instance_boxes every plane (sample, frame) is compacted on its own.
+
+    Returns device tensors, int32, with the table's leading dimensions [...]: slot_ids [..., max_nodes] (-1 past count),
+    boxes [..., max_nodes, 4] pixel edges (x_min, y_min, x_max + 1, y_max + 1) and areas [..., max_nodes] (zero past count),
+    count [...], overflow [...] (1: the plane holds more than max_nodes such ids; the rest is dropped).  Nothing is read back."""
+    max_nodes, min_pixels = _link_nodes(max_nodes, min_pixels)
+    id_lo, id_hi = (int(v) for v in id_range)
+    if not 0 <= id_lo < id_hi:
+        raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if table.dim() < 2 or tuple(table.shape[-2:]) != (id_hi - id_lo, 5):
+        raise ValueError(f"table must be [..., {id_hi - id_lo}, 5] for id_range {id_range}, got {list(table.shape)}")
+    lead = tuple(table.shape[:-2])
+    table = _link_i32("table", table, table.shape)
+    planes = 1
+    for n in lead:
+        planes *= n
+    dev = table.device
+    slot_ids = torch.empty(lead + (max_nodes,), device=dev, dtype=torch.int32)
+    boxes = torch.empty(lead + (max_nodes, 4), device=dev, dtype=torch.int32)
+    areas = torch.empty(lead + (max_nodes,), device=dev, dtype=torch.int32)
+    count = torch.empty(lead, device=dev, dtype=torch.int32)
+    overflow = torch.empty(lead, device=dev, dtype=torch.int32)
+    if planes:
+        _lib.check(_lib.lib().c2m_instance_slots(_p(table), _p(slot_ids), _p(boxes), _p(areas), _p(count), _p(overflow), planes,
+                                                 id_hi - id_lo, id_lo, min_pixels, max_nodes, _stream()), "instance_slots")
+    return slot_ids, boxes, areas, count, overflow
+
+
+def instance_overlap(ref, frame, flow, ref_slots, ref_count, frame_slots, frame_count):
+    """Contingency table of two instance maps: pairs [P, max_nodes + 1, max_nodes + 1] int32 on the device, pairs[p, i, j] = the
+    number of pixels q of frame[p] whose id is frame_slots[p, j] and whose source pixel in ref[p] holds ref_slots[p, i]; the last
+    row / column count the pixels without a slot (background, stuff, below min_pixels).
+
+    ref, frame [P,H,W] int32; flow [P,2,H,W] fp32 in pixels, defined on the frame's pixels and pointing into ref -- the source
+    pixel is the one label_warp reads (same coordinates, border clamp, ties to even) -- or None: the source pixel is q itself
+    (plain overlap; no coordinate is computed).  ref_slots / frame_slots [P, max_nodes] and ref_count /
+    frame_count [P]: instance_slots of the two maps.  One pass over the pixels, int32 atomics only: bit-repeatable."""
+    if not isinstance(ref, torch.Tensor) or ref.dim() != 3:
+        raise ValueError(f"ref must be [P,H,W], got {list(getattr(ref, 'shape', ()))}")
+    P, H, W = ref.shape
+    if not isinstance(ref_slots, torch.Tensor) or ref_slots.dim() != 2:
+        raise ValueError(f"ref_slots must be [P, max_nodes], got {list(getattr(ref_slots, 'shape', ()))}")
+    M, _ = _link_nodes(ref_slots.shape[1])
+    ref, frame = _link_i32("ref", ref, (P, H, W)), _link_i32("frame", frame, (P, H, W))
+    ref_slots, frame_slots = _link_i32("ref_slots", ref_slots, (P, M)), _link_i32("frame_slots", frame_slots, (P, M))
+    ref_count, frame_count = _link_i32("ref_count", ref_count, (P,)), _link_i32("frame_count", frame_count, (P,))
+    if H * W >= 2 ** 31:
+        raise ValueError(f"a plane of {H}x{W} pixels is too large (H * W must be below 2**31)")
+    if flow is not None:
+        if not flow.is_cuda:
+            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+        if flow.dtype != torch.float32:
+            raise TypeError(f"flow must be fp32 (coordinates are never rounded), got {flow.dtype}")
+        if tuple(flow.shape) != (P, 2, H, W):
+            raise ValueError(f"flow must be {[P, 2, H, W]} (at the size of the maps), got {list(flow.shape)}")
+        if flow.device.index != _cur_device():
+            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{flow.device.index} but the current device is cuda:{_cur_device()}")
+        flow = _f(flow.detach())
+    pairs = torch.empty(P, M + 1, M + 1, device=ref.device, dtype=torch.int32)
+    if P:
+        _lib.check(_lib.lib().c2m_instance_overlap(_p(ref), _p(frame), _p(flow), _p(ref_slots), _p(ref_count), _p(frame_slots),
+                                                   _p(frame_count), _p(pairs), P, H, W, M, _stream()), "instance_overlap")
+    return pairs
+
+
+def instance_match(pairs, ref_slots, ref_count, frame_slots, frame_count, min_iou=(1, 4), same_class=True):
+    """Mutual best match of an instance_overlap table: link [P, max_nodes] int32 on the device, the frame slot of every ref slot
+    or -1.  With r_i / a_j the row / column sums of pairs[p] and IoU(i, j) = n_ij / (r_i + a_j - n_ij), frame slot j is linked to
+    ref slot i iff i has the largest IoU in column j, j has the largest IoU in row i (cells with n = 0 never count, ties go to the
+    lower id), IoU >= min_iou = (num, den), exactly equal passing, and -- with same_class -- both ids have the same id // 1000.
+    Integer arithmetic throughout (64-bit cross-multiplication)."""
+    if not isinstance(ref_slots, torch.Tensor) or ref_slots.dim() != 2:
+        raise ValueError(f"ref_slots must be [P, max_nodes], got {list(getattr(ref_slots, 'shape', ()))}")
+    P = ref_slots.shape[0]
+    M, _ = _link_nodes(ref_slots.shape[1])
+    try:
+        num, den = (int(v) for v in min_iou)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_iou must be a rational (num, den) of two integers, got {min_iou!r}") from None
+    if tuple(min_iou) != (num, den) or not (0 <= num <= den and 1 <= den < 2 ** 31):
+        raise ValueError(f"min_iou must be a rational (num, den) of two integers with 0 <= num <= den, got {min_iou!r}")
+    pairs = _link_i32("pairs", pairs, (P, M + 1, M + 1))
+    ref_slots, frame_slots = _link_i32("ref_slots", ref_slots, (P, M)), _link_i32("frame_slots", frame_slots, (P, M))
+    ref_count, frame_count = _link_i32("ref_count", ref_count, (P,)), _link_i32("frame_count", frame_count, (P,))
+    link = torch.empty(P, M, device=pairs.device, dtype=torch.int32)
+    if P:
+        _lib.check(_lib.lib().c2m_instance_match(_p(pairs), _p(ref_slots), _p(ref_count), _p(frame_slots), _p(frame_count),
+                                                 _p(link), P, M, num, den, 1 if same_class else 0, _stream()), "instance_match")
+    return link
+
+
 def occlusion_splat(flow, want_map=True, want_clip=False):
     """get_occlusion_map for [B,2,H,W] or, frame-batched, [B,2,T,H,W] flows -> ([B,1,(T,)H,W] map, clip_mask) ."""
     _dev(flow)

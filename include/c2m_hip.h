@@ -395,6 +395,33 @@ int c2m_instance_stats(const int32_t* instance, int32_t* table, int B, int T, in
 int c2m_instance_compact(const int32_t* table, int32_t* ids, int32_t* boxes, int32_t* count, int32_t* overflow, int B,
                          int t_in, int nid, int id_lo, int min_pixels, int max_nodes, void* stream);
 
+/* Linking the objects of two instance maps that do not share ids (instance_link.hip; c2m_amd.tracking).  The reference reads an
+ * id column per frame from tracker files instead.  Integer arithmetic after the source coordinate, int32 atomics only:
+ * bit-repeatable.  max_nodes <= c2m_instance_link_max_nodes() (64: one lane per slot) in all three.
+ * c2m_instance_slots: per plane of a c2m_instance_stats table [planes][nid][5], the ids with count >= min_pixels (>= 1),
+ *   ascending; an id's position is its SLOT.  slot_ids[planes][max_nodes] (-1 past count), boxes[planes][max_nodes][4] =
+ *   {x_min, y_min, x_max+1, y_max+1} and areas[planes][max_nodes] (zero past count), count[planes] (<= max_nodes),
+ *   overflow[planes] = 1 when the plane has more than max_nodes such ids.
+ * c2m_instance_overlap: ref, frame [P][H][W] int32; flow [P][2][H][W] fp32 in pixels, defined on the frame's pixels and pointing
+ *   into the ref plane, or NULL; the slot lists and counts of both planes as c2m_instance_slots wrote them.
+ *   pairs[P][max_nodes+1][max_nodes+1] (written in full) : pairs[p][i][j] = number of frame pixels q whose id has frame slot j
+ *   and whose source pixel holds an id with ref slot i; index max_nodes = "no slot".  The source pixel is the one c2m_label_warp
+ *   reads for q (same coordinates, border clamp, round half to even); with flow == NULL it is q itself (plain overlap, no
+ *   coordinate is computed).  H * W < 2^31.
+ * c2m_instance_match: link[P][max_nodes] = the frame slot of every ref slot, or -1.  With r_i / a_j the row / column sums of
+ *   pairs (all max_nodes+1 cells) and IoU(i,j) = n_ij / (r_i + a_j - n_ij): j is linked to i iff i has the largest IoU of column j,
+ *   j has the largest IoU of row i (cells with n = 0 never count; ties go to the lower slot), IoU * iou_den >= iou_num, and,
+ *   with same_class != 0, ref id / 1000 == frame id / 1000.  Fractions are compared by 64-bit cross-multiplication.        */
+int c2m_instance_link_max_nodes(void);
+int c2m_instance_slots(const int32_t* table, int32_t* slot_ids, int32_t* boxes, int32_t* areas, int32_t* count,
+                       int32_t* overflow, int planes, int nid, int id_lo, int min_pixels, int max_nodes, void* stream);
+int c2m_instance_overlap(const int32_t* ref, const int32_t* frame, const float* flow, const int32_t* ref_slots,
+                         const int32_t* ref_count, const int32_t* frame_slots, const int32_t* frame_count, int32_t* pairs,
+                         int P, int H, int W, int max_nodes, void* stream);
+int c2m_instance_match(const int32_t* pairs, const int32_t* ref_slots, const int32_t* ref_count, const int32_t* frame_slots,
+                       const int32_t* frame_count, int32_t* link, int P, int max_nodes, int iou_num, int iou_den,
+                       int same_class, void* stream);
+
 /* ---- rendering (render.hip): results as uint8 pictures on the device ------------------------------------------------
  * A SHEET is uint8 [T][rows*H][cols*W][C] (HWC); sample b sits in cell (b / cols, b % cols), as the reference's merge
  * (utils/utils.py:26-43) lays samples out; cells without a sample hold zero input.  B <= rows * cols.  Inputs are dense
