@@ -19,6 +19,7 @@ ARCH = "gfx950"
 NOSLP = ["-fno-slp-vectorize"]
 SOURCES = {"conv_igemm.hip": NOSLP, "conv_nc8.hip": NOSLP, "conv_wino.hip": NOSLP, "conv_wino4.hip": NOSLP, "conv_ring.hip": NOSLP, "norm.hip": NOSLP, "losses.hip": NOSLP,
            "optim.hip": ["-ffp-contract=off"] + NOSLP, "data_prep.hip": ["-ffp-contract=off"] + NOSLP,
+           "resize.hip": ["-ffp-contract=off"] + NOSLP,
            "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
            "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],

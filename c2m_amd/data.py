@@ -2,12 +2,15 @@
 
 Reference: src/datasets/cityscapes.py builds every sample on the CPU -- ToTensor of the frames (:30-33), the 20-channel
 one-hot split of the label-id map (:35-41), instance ids (:43-52), occlusion PNG -> clip_mask (:212-216, 262-265), .flo
-HWC -> CHW (:219-231) -- and src/train.py:23-38 collates.  Here the decoded arrays (what PIL / np.fromfile return, after
-the resize) are uploaded as they are (uint8 / int32 / float32) and expanded on the device by three small kernels; the
-result is the batch dict `GeneratorFullModel.forward` consumes.  File decoding / PIL resizing stay on the host."""
+HWC -> CHW (:219-231) -- and src/train.py:23-38 collates.  Here the decoded arrays (what PIL / np.fromfile return, at
+dataset resolution or already at input_size) are uploaded as they are (uint8 / int32 / float32), resized on the device
+where asked (`size=`: resize_frames is Pillow's BICUBIC and resize_maps its NEAREST bit for bit, resize_flow is
+transforms.Resize on the .flo tensor times size[0] / h; csrc/resize.hip) and expanded by three small kernels; the result is
+the batch dict `GeneratorFullModel.forward` consumes.  Only file decoding stays on the host."""
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _p, _stream
 
 
@@ -66,9 +69,68 @@ def prep_flow_occ(occ_u8, flow_hwc):
     return occ, flow
 
 
+def _size(size):
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (h, w), got {size!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"size must be positive, got {size!r}")
+    return h, w
+
+
+def _resize(x, name, dtypes, tail, size, run):
+    """Shared front of the three resizes: x is [..., H, W] + tail dims; checks first, then one launch on the flattened batch."""
+    if not torch.is_tensor(x) or x.dtype not in dtypes:
+        raise TypeError(f"{name} must be a tensor of dtype {' or '.join(str(d) for d in dtypes)}")
+    _dev(x)
+    h, w = _size(size)
+    cut = x.dim() - len(tail)                                  # [..., H, W] ends here
+    if cut < 2 or any(c not in ok for c, ok in zip(x.shape[cut:], tail)):
+        raise ValueError(f"{name} must be [..., H, W{''.join(', ' + '|'.join(map(str, ok)) for ok in tail)}], got "
+                         f"{tuple(x.shape)}")
+    lead, (H, W), rest = x.shape[:cut - 2], x.shape[cut - 2:cut], x.shape[cut:]
+    if (H, W) == (h, w):
+        return x                                              # already at size: no launch
+    if x.numel() == 0:
+        if H < 1 or W < 1:
+            raise ValueError(f"{name} has an empty image: {tuple(x.shape)}")
+        return x.new_empty(*lead, h, w, *rest)
+    return run(x.contiguous().reshape(-1, H, W, *rest), (h, w)).reshape(*lead, h, w, *rest)
+
+
+def resize_frames(frames_u8, size, filter="bicubic"):
+    """[..., H, W, C] uint8 (C in {1, 3}, HWC as PIL decodes it) -> [..., h, w, C] with size = (h, w): what
+    Image.resize((w, h), BICUBIC) returns (cityscapes.py:23,33), bit for bit; filter 'bilinear' is Pillow's BILINEAR."""
+    if filter not in ("bicubic", "bilinear"):
+        raise ValueError(f"filter must be 'bicubic' or 'bilinear', got {filter!r} (LANCZOS is not supported)")
+    return _resize(frames_u8, "frames", (torch.uint8,), ((1, 3),), size, lambda x, s: ops.resize_u8(x, s, filter))
+
+
+def resize_maps(x, size):
+    """[..., H, W] uint8 (label ids, occlusion) or int32 (instance ids) -> [..., h, w]: Image.resize((w, h), NEAREST)
+    (cityscapes.py:26-33,211), bit for bit."""
+    return _resize(x, "maps", (torch.uint8, torch.int32), (), size, ops.resize_nearest)
+
+
+def resize_flow(flow_hwc, size, antialias=False):
+    """[..., H, W, 2] float32 (the .flo layout) -> [..., h, w, 2]: transforms.Resize on the tensor times h / H on BOTH
+    channels (cityscapes.py:220-222).  antialias=False: plain bilinear, align_corners=False (Resize on tensors in the
+    torchvision of the reference's time); True: the triangle filter widened by the scale (torchvision >= 0.17)."""
+    return _resize(flow_hwc, "flow", (torch.float32,), ((2,),), size, lambda x, s: ops.resize_flow(x, s, bool(antialias)))
+
+
 def assemble_batch(frames_u8, labels_u8, instance_i32, target_occ_u8, target_flow_hwc, tracking_gnn,
-                   input_occ_u8=None, input_flow_hwc=None):
-    """The batch dict of model.py:124 from decoded arrays already on the device.  `instance_i32` [B,T,H,W] int32."""
+                   input_occ_u8=None, input_flow_hwc=None, size=None, antialias=False):
+    """The batch dict of model.py:124 from decoded arrays already on the device.  `instance_i32` [B,T,H,W] int32.
+    size = (h, w): every array may be at dataset resolution and is resized first (resize_frames / resize_maps / resize_flow
+    with `antialias`); None: the arrays are at input_size already."""
+    if size is not None:
+        fl = lambda t: None if t is None else resize_flow(t, size, antialias)
+        mp = lambda t: None if t is None else resize_maps(t, size)
+        frames_u8, labels_u8, instance_i32 = resize_frames(frames_u8, size), mp(labels_u8), mp(instance_i32.to(torch.int32))
+        target_occ_u8, input_occ_u8, target_flow_hwc, input_flow_hwc = mp(target_occ_u8), mp(input_occ_u8), \
+            fl(target_flow_hwc), fl(input_flow_hwc)
     bg, fg = prep_seg_onehot(labels_u8)
     occ, flow = prep_flow_occ(target_occ_u8, target_flow_hwc)
     batch = dict(video=prep_video(frames_u8), bg_mask=bg, fg_mask=fg,

@@ -3012,3 +3012,120 @@ def norm_apply_eval(x, mean, invstd, gamma, beta, act=None):
     _lib.check(_lib.lib().c2m_norm_apply(_p(x), _p(_f(mean)), _p(_f(invstd)), _p(gamma), _p(beta), None, _p(y), None, N, C, S, 1,
                                          ACT[act], LRELU_SLOPE, _dt(x), _stream()), "norm_apply(eval)")
     return y
+
+
+# ------------------------------------------------------------------ dataset resolution -> input_size (csrc/resize.hip)
+# Per-axis tables, built in float64 exactly as the library that defines the result builds them, cached per (in, out, filter)
+# and per device.  Pillow (src/libImaging/Resample.c precompute_coeffs / normalize_coeffs_8bpc, Geometry.c ImagingScaleAffine) for
+# uint8 images and maps; torch's upsample_bilinear2d (align_corners=False) and its antialiased form for flow fields.
+_RESIZE_FILTERS = {"bilinear": 1.0, "bicubic": 2.0}
+_resize_tables = {}
+
+
+def _resize_filter_value(name, x):
+    x = np.abs(x)
+    if name == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1,
+                    np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def _resize_coeffs(n_in, n_out, name):
+    """precompute_coeffs: bounds [out,2] int32 (first, count) and normalised float64 coefficients [out,ks]."""
+    scale = float(n_in) / n_out
+    filterscale = max(scale, 1.0)
+    support = _RESIZE_FILTERS[name] * filterscale
+    ks = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    ss = 1.0 / filterscale
+    first = np.maximum((center - support + 0.5).astype(np.int64), 0)            # (int): towards zero, as astype
+    count = np.minimum((center + support + 0.5).astype(np.int64), n_in) - first
+    x = np.arange(ks, dtype=np.int64)[None, :]
+    w = _resize_filter_value(name, ((x + first[:, None]) - center[:, None] + 0.5) * ss)
+    w = np.where(x < count[:, None], w, 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]                                             # the running sum `ww += w`, in tap order
+    k = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    return np.ascontiguousarray(np.stack([first, count], 1).astype(np.int32)), k, ks
+
+
+def _resize_bilinear_taps(n_in, n_out):
+    """upsample_bilinear2d, align_corners=False: source = scale * (dst + 0.5) - 0.5 clamped at 0, the two neighbours."""
+    scale = float(n_in) / n_out
+    src = np.maximum(scale * (np.arange(n_out, dtype=np.float64) + 0.5) - 0.5, 0.0)
+    i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+    lam = src - i0
+    two = i0 + 1 <= n_in - 1
+    bounds = np.stack([i0, np.where(two, 2, 1)], 1).astype(np.int32)
+    k = np.stack([np.where(two, 1.0 - lam, 1.0), np.where(two, lam, 0.0)], 1)
+    return np.ascontiguousarray(bounds), k, 2
+
+
+def _resize_nearest_index(n_in, n_out):
+    """ImagingScaleAffine: xo = 0.5 * a; index = (int)xo; xo += a, a running double sum; outside the image: -1."""
+    a = float(n_in) / n_out
+    xo = np.cumsum(np.concatenate([[0.5 * a], np.full(n_out - 1, a)]))
+    idx = xo.astype(np.int64)
+    return np.ascontiguousarray(np.where((xo < 0.0) | (idx >= n_in), -1, idx).astype(np.int32))
+
+
+def resize_table(kind, n_in, n_out, device):
+    """(host arrays, device tensors, ks) of one axis.  kind: 'bicubic' / 'bilinear' (Pillow 8-bit: bounds + int32 coefficients),
+    'nearest' (index), 'flow' / 'flow_aa' (bounds + fp32 weights)."""
+    key = (kind, int(n_in), int(n_out), torch.device(device))
+    tab = _resize_tables.get(key)
+    if tab is None:
+        if kind in _RESIZE_FILTERS:
+            bounds, k, ks = _resize_coeffs(n_in, n_out, kind)
+            q = k * (1 << 22)
+            host = (bounds, np.ascontiguousarray(np.where(k < 0, -0.5 + q, 0.5 + q).astype(np.int32)))
+        elif kind == "nearest":
+            host, ks = (_resize_nearest_index(n_in, n_out),), 1
+        elif kind in ("flow", "flow_aa"):
+            bounds, k, ks = _resize_coeffs(n_in, n_out, "bilinear") if kind == "flow_aa" else _resize_bilinear_taps(n_in, n_out)
+            host = (bounds, np.ascontiguousarray(k.astype(np.float32)))
+        else:
+            raise ValueError(f"unknown resize table {kind!r}")
+        tab = _resize_tables[key] = (host, tuple(torch.from_numpy(h).to(device) for h in host), ks)
+    return tab
+
+
+def _hp(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def resize_u8(x, size, filter="bicubic"):
+    """[N,Hin,Win,C] uint8 (C in {1, 3}), contiguous, on the device -> [N,h,w,C]: Pillow's Image.resize, bit for bit."""
+    N, Hin, Win, C = x.shape
+    h, w = size
+    (bxh, _), (bx, kx), ksx = resize_table(filter, Win, w, x.device)
+    (byh, _), (by, ky), ksy = resize_table(filter, Hin, h, x.device)
+    out = torch.empty(N, h, w, C, device=x.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().c2m_resize_u8(_p(x), _p(out), N, Hin, Win, h, w, C, _hp(bxh), _p(bx), _p(kx), ksx, _hp(byh), _p(by),
+                                        _p(ky), ksy, _stream()), "resize_u8")
+    return out
+
+
+def resize_nearest(x, size):
+    """[N,Hin,Win] uint8 or int32, contiguous, on the device -> [N,h,w]: Pillow's Image.resize(NEAREST)."""
+    N, Hin, Win = x.shape
+    h, w = size
+    (xh,), (xi,), _ = resize_table("nearest", Win, w, x.device)
+    (yh,), (yi,), _ = resize_table("nearest", Hin, h, x.device)
+    out = torch.empty(N, h, w, device=x.device, dtype=x.dtype)
+    _lib.check(_lib.lib().c2m_resize_nearest(_p(x), _p(out), x.element_size(), N, Hin, Win, h, w, _hp(xh), _p(xi), _hp(yh),
+                                             _p(yi), _stream()), "resize_nearest")
+    return out
+
+
+def resize_flow(x, size, antialias=False):
+    """[N,Hin,Win,2] float32, contiguous, on the device -> [N,h,w,2]: triangle filter, then * h / Hin on both channels."""
+    N, Hin, Win, _ = x.shape
+    h, w = size
+    kind = "flow_aa" if antialias else "flow"
+    (bxh, _), (bx, kx), ksx = resize_table(kind, Win, w, x.device)
+    (byh, _), (by, ky), ksy = resize_table(kind, Hin, h, x.device)
+    out = torch.empty(N, h, w, 2, device=x.device, dtype=torch.float32)
+    _lib.check(_lib.lib().c2m_resize_flow(_p(x), _p(out), N, Hin, Win, h, w, _hp(bxh), _p(bx), _p(kx), ksx, _hp(byh), _p(by),
+                                          _p(ky), ksy, _stream()), "resize_flow")
+    return out

@@ -223,16 +223,17 @@ def scene_graphs(tr, size, num_input_frames, lambda_traj=1):
 
 
 def tracked_batch(frames_u8, labels_u8, instance_i32, target_occ_u8, target_flow_hwc, num_input_frames, input_occ_u8=None,
-                  input_flow_hwc=None, lambda_traj=1, config=None, **track_kw):
+                  input_flow_hwc=None, lambda_traj=1, config=None, size=None, antialias=False, **track_kw):
     """data.assemble_batch without tracker files: its inputs minus tracking_gnn (decoded arrays on the device) plus
     num_input_frames -> the same batch dict, with `tracking_gnn` built from the instance maps and the batch's own flows
     (track_instances on instance_mask, target_bw_of and input_of), `tracking_mask` [B,1,T,H,W] (graph.tracking_mask per sample)
-    and `tracks` (the Tracks).  config: the run's configuration, checked by check_config.  track_kw: track_instances."""
+    and `tracks` (the Tracks).  config: the run's configuration, checked by check_config.  size, antialias: as assemble_batch
+    (arrays at dataset resolution are resized on the device first).  track_kw: track_instances."""
     from .data import assemble_batch
     if config is not None:
         check_config(config)
     batch = assemble_batch(frames_u8, labels_u8, instance_i32, target_occ_u8, target_flow_hwc, None, input_occ_u8,
-                           input_flow_hwc)
+                           input_flow_hwc, size=size, antialias=antialias)
     inst = batch["instance_mask"]
     tr = track_instances(inst, num_input_frames, batch["target_bw_of"], batch["input_of"], **track_kw)
     tracking_ids, graphs = scene_graphs(tr, tuple(inst.shape[-2:]), num_input_frames, lambda_traj)

@@ -382,6 +382,27 @@ int c2m_prep_seg_onehot(const uint8_t* labels_bthw, float* bg_mask, float* fg_ma
 int c2m_prep_flow_occ(const uint8_t* occ_bthw, const float* flow_bthwc, float* occ_out, float* flow_out, int B, int T,
                       int H, int W, void* stream);
 
+/* Dataset resolution -> train_params.input_size (resize.hip): src/datasets/cityscapes.py:23-33,211 (PIL Image.resize, BICUBIC for
+ * frames, NEAREST for label / instance / occlusion maps) and :220-222 (transforms.Resize on the .flo tensor, * size[0] / h).
+ * Every table is built by the caller per axis and passed twice: *_host (read by the entry point: checked, and used to size the
+ * tile) and the same values on the device (read by the kernel).  Dense arrays; a launch each; no allocation, no atomics.
+ * c2m_resize_u8: [N][Hin][Win][C] uint8, C in {1, 3} -> [N][Hout][Wout][C], Pillow's 8-bit resampler bit for bit: bounds[out][2]
+ *   = (first, count) and coef[out][ks] int32 (precompute_coeffs + normalize_coeffs_8bpc: 22 fractional bits), each pass
+ *   clip8((2^21 + sum p * k) >> 22), horizontal first, uint8 between the passes.  count in [1, ks], bounds non-decreasing.
+ * c2m_resize_nearest: [N][Hin][Win] of 1- or 4-byte elements -> [N][Hout][Wout] through index[out] (source column / row, or -1:
+ *   zero), Pillow's NEAREST.
+ * c2m_resize_flow: [N][Hin][Win][2] fp32 -> [N][Hout][Wout][2], separable filter with fp32 weights weight[out][ks], fp32
+ *   accumulation in a fixed order (row dot products left to right, then top to bottom), then (v * Hout) / Hin on both channels. */
+int c2m_resize_u8(const uint8_t* src, uint8_t* dst, int N, int Hin, int Win, int Hout, int Wout, int C,
+                  const int32_t* bounds_x_host, const int32_t* bounds_x, const int32_t* coef_x, int ksx,
+                  const int32_t* bounds_y_host, const int32_t* bounds_y, const int32_t* coef_y, int ksy, void* stream);
+int c2m_resize_nearest(const void* src, void* dst, int elem_bytes, long N, int Hin, int Win, int Hout, int Wout,
+                       const int32_t* index_x_host, const int32_t* index_x, const int32_t* index_y_host, const int32_t* index_y,
+                       void* stream);
+int c2m_resize_flow(const float* src, float* dst, long N, int Hin, int Win, int Hout, int Wout, const int32_t* bounds_x_host,
+                    const int32_t* bounds_x, const float* weight_x, int ksx, const int32_t* bounds_y_host,
+                    const int32_t* bounds_y, const float* weight_y, int ksy, void* stream);
+
 /* Per-instance boxes of the input frames, for graphs built from instance maps instead of tracker files (click-to-move;
  * c2m_amd.interactive).  The reference has no counterpart: it reads per-object tracker boxes (cityscapes.py:79-199).
  * c2m_instance_stats: instance [B][T][H][W] int32, planes = (sample, input frame t < t_in); for every id in [id_lo, id_hi)
