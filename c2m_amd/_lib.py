@@ -63,6 +63,11 @@ _SIGS = {
     "c2m_resize_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p]),
     "c2m_resize_nearest": (c_int, [c_void_p, c_void_p, c_int, c_long] + [c_int] * 4 + [c_void_p] * 5),
     "c2m_resize_flow": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p]),
+    "c2m_detect_input": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_long] * 4 + [c_int, c_int, c_void_p]),
+    "c2m_yolo_candidates": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float, c_int] + [c_void_p] * 5),
+    "c2m_nms_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "c2m_match_detections": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                     c_void_p, c_long, c_int, c_int, c_int, c_double, c_double] + [c_void_p] * 4),
     "c2m_instance_stats": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "c2m_instance_compact": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
     "c2m_instance_link_max_nodes": (c_int, []),

@@ -23,7 +23,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_nc8.hip": NOSLP, "conv_wino.hip": NOSL
            "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
            "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],
-           "render.hip": ["-ffp-contract=off"] + NOSLP,
+           "render.hip": ["-ffp-contract=off"] + NOSLP, "detect.hip": ["-ffp-contract=off"] + NOSLP,
            "flownet_ops.hip": ["-ffp-contract=off"] + NOSLP, "gnn.hip": ["-ffp-contract=off"] + NOSLP}
 
 

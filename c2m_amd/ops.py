@@ -3129,3 +3129,166 @@ def resize_flow(x, size, antialias=False):
     _lib.check(_lib.lib().c2m_resize_flow(_p(x), _p(out), N, Hin, Win, h, w, _hp(bxh), _p(bx), _p(kx), ksx, _hp(byh), _p(by),
                                           _p(ky), ksy, _stream()), "resize_flow")
     return out
+
+
+# ========================================================================================== detector metric (csrc/detect.hip)
+DETECT_SIZE = 416
+_DET_MAX_HEADS, _DET_MAX_ANCHORS = 4, 8
+
+
+def _det_check(name, t, dtype, dim=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"c2m_amd ops need tensors on a HIP device (no CPU fallback by design): {name} is on {t.device}")
+    if t.device.index != _cur_device():
+        raise RuntimeError(f"c2m_amd ops: {name} on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if dim is not None and t.dim() != dim:
+        raise ValueError(f"{name} must have {dim} dimensions, got {tuple(t.shape)}")
+
+
+def detect_scale(width):
+    """The reference's rule (utils_yolov3.py:69): frames 256 or 320 wide go in as they are, every other width doubled."""
+    return 1 if width in (256, 320) else 2
+
+
+def detect_input(frames, size=DETECT_SIZE):
+    """frames [B,C,H,W] fp32, or a video [B,C,T,H,W] whose LAST time index is read through its strides (no copy) ->
+    ([B,C,size,size], scale, (h, w)): nearest x scale, zeros to the right and below -- and a crop where the scaled frame is
+    larger than `size`, as F.pad with a negative pad does.  (h, w) is the scaled, unpadded frame size.  One launch."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() not in (4, 5):
+        raise ValueError("frames must be a [B,C,H,W] or [B,C,T,H,W] tensor")
+    _det_check("frames", frames, torch.float32)
+    v = frames.detach()
+    if v.dim() == 5:
+        if v.shape[2] < 1:
+            raise ValueError("the video has no frame")
+        v = v[:, :, -1]
+    B, C, H, W = v.shape
+    if min(C, H, W) < 1:
+        raise ValueError(f"empty frame {tuple(v.shape)}")
+    if any(s < 0 for s in v.stride()):
+        v = v.contiguous()
+    s = detect_scale(W)
+    out = torch.empty(B, C, size, size, device=v.device, dtype=torch.float32)
+    if B:
+        _lib.check(_lib.lib().c2m_detect_input(_p(v), _p(out), B, C, H, W, v.stride(0), v.stride(1), v.stride(2), v.stride(3), s,
+                                               size, _stream()), "detect_input")
+    return out, s, (H * s, W * s)
+
+
+def _yolo_plan(heads, anchors, num_classes, img_size):
+    if not isinstance(heads, (list, tuple)) or not 1 <= len(heads) <= _DET_MAX_HEADS:
+        raise ValueError(f"heads must be a list of 1..{_DET_MAX_HEADS} head maps")
+    if len(anchors) != len(heads):
+        raise ValueError(f"{len(heads)} heads but {len(anchors)} anchor sets")
+    C = int(num_classes)
+    if C < 1:
+        raise ValueError("num_classes must be >= 1")
+    N = None
+    grid, na, boxes = [], [], 0
+    for i, (h, a) in enumerate(zip(heads, anchors)):
+        _det_check(f"heads[{i}]", h, torch.float32, 4)
+        if not 1 <= len(a) <= _DET_MAX_ANCHORS or any(len(p) != 2 for p in a):
+            raise ValueError(f"anchors[{i}] must be 1..{_DET_MAX_ANCHORS} (w, h) pairs")
+        n, ch, gy, gx = h.shape
+        if N is None:
+            N = n
+        if n != N or gy != gx or gy < 1 or ch != len(a) * (5 + C):
+            raise ValueError(f"heads[{i}] must be [{N},{len(a) * (5 + C)},g,g] for {len(a)} anchors and {C} classes, "
+                             f"got {tuple(h.shape)}")
+        grid.append(gy)
+        na.append(len(a))
+        boxes += len(a) * gy * gy
+    if img_size < 1:
+        raise ValueError("img_size must be positive")
+    return N, C, grid, na, boxes
+
+
+def yolo_candidates(heads, anchors, num_classes, img_size, conf_thres=0.5):
+    """YOLOLayer decode + confidence filter + class arg-max of every head of every image.  heads: raw maps [N, A*(5+C), g, g];
+    anchors: per head a list of (w, h) in pixels; img_size: the side of the detector's input.  Returns cand [N,cap,7] =
+    (x1, y1, x2, y2, conf, class_conf, class) compacted in box order (head, anchor, row, column), score [N,cap] = conf *
+    class_conf with -inf in the unused slots, count [N] int32.  cap = every box: nothing is dropped."""
+    N, C, grid, na, boxes = _yolo_plan(heads, anchors, num_classes, img_size)
+    dev = heads[0].device
+    cap = boxes
+    cand = torch.zeros(N, cap, 7, device=dev, dtype=torch.float32)
+    score = torch.full((N, cap), float("-inf"), device=dev, dtype=torch.float32)
+    count = torch.zeros(N, device=dev, dtype=torch.int32)
+    if N == 0:
+        return cand, score, count
+    hs = [_f(h.detach()) for h in heads]
+    nh = len(hs)
+    ptrs = (ctypes.c_void_p * nh)(*[h.data_ptr() for h in hs])
+    stride = [img_size / g for g in grid]                                      # YOLOLayer.compute_grid_offsets: a Python float
+    anc = np.zeros((nh, _DET_MAX_ANCHORS, 2), np.float32)
+    for i, a in enumerate(anchors):
+        for j, (w, h) in enumerate(a):
+            anc[i, j] = (w / stride[i], h / stride[i])                         # FloatTensor([(a_w / stride, a_h / stride)])
+    g_arr, na_arr = (ctypes.c_int * nh)(*grid), (ctypes.c_int * nh)(*na)
+    st_arr = (ctypes.c_float * nh)(*stride)
+    ws = torch.empty(N * _cdiv(boxes, 256), device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().c2m_yolo_candidates(ptrs, g_arr, na_arr, st_arr, _hp(anc), _DET_MAX_ANCHORS, nh, N, C,
+                                              float(conf_thres), cap, _p(ws), _p(cand), _p(score), _p(count), _stream()),
+               "yolo_candidates")
+    return cand, score, count
+
+
+def nms_merge(cand, score, count, nms_thres=0.4):
+    """The reference's suppress-and-merge loop for every image in one launch.  Candidates are ordered by descending score with a
+    STABLE sort (ties: lower box index first).  Returns dets [N,cap,7] (rows >= kept[n] are zero) and kept [N] int32."""
+    _det_check("cand", cand, torch.float32, 3)
+    _det_check("score", score, torch.float32, 2)
+    _det_check("count", count, torch.int32, 1)
+    N, cap, seven = cand.shape
+    if seven != 7 or tuple(score.shape) != (N, cap) or tuple(count.shape) != (N,) or cap < 1:
+        raise ValueError(f"need cand [N,cap,7], score [N,cap], count [N]; got {tuple(cand.shape)}, {tuple(score.shape)}, "
+                         f"{tuple(count.shape)}")
+    dets = torch.zeros(N, cap, 7, device=cand.device, dtype=torch.float32)
+    kept = torch.zeros(N, device=cand.device, dtype=torch.int32)
+    if N == 0:
+        return dets, kept
+    order = torch.sort(score, dim=1, descending=True, stable=True).indices
+    srt = torch.gather(_f(cand), 1, order.unsqueeze(-1).expand(N, cap, 7))
+    _lib.check(_lib.lib().c2m_nms_merge(_p(srt), _p(_f(count)), N, cap, float(nms_thres), _p(dets), _p(kept), _stream()),
+               "nms_merge")
+    return dets, kept
+
+
+def match_detections(dets, kept, index, roi, x, batch, scale, size):
+    """find_best_detection + the trajectory error for every clicked object in one launch.  dets [2B,cap,7] / kept [2B]: ground
+    truth images first, predicted second; index [M] int64 node indices; roi [nodes,T,4], x [nodes,t_in,F] fp32 and batch [nodes]
+    int64 from the graph; size = (h, w) of the scaled, unpadded frame.  Returns flags [M,3] int32 (skipped, gt_found,
+    pred_found; skipped = -1 marks an index outside the graph), boxes [M,8] int32, err [M,2] float64."""
+    _det_check("dets", dets, torch.float32, 3)
+    _det_check("kept", kept, torch.int32, 1)
+    _det_check("index", index, torch.int64, 1)
+    _det_check("roi", roi, torch.float32, 3)
+    _det_check("x", x, torch.float32, 3)
+    _det_check("batch", batch, torch.int64, 1)
+    N2, cap, seven = dets.shape
+    nodes = batch.shape[0]
+    if seven != 7 or N2 % 2 or N2 < 2 or kept.shape[0] != N2 or cap < 1:
+        raise ValueError(f"need dets [2B,cap,7] and kept [2B], got {tuple(dets.shape)} and {tuple(kept.shape)}")
+    if roi.shape[0] != nodes or roi.shape[2] != 4 or roi.shape[1] < 1:
+        raise ValueError(f"roi must be [{nodes},T,4], got {tuple(roi.shape)}")
+    if x.shape[0] != nodes or x.shape[1] < 1 or x.shape[2] < 2:
+        raise ValueError(f"x must be [{nodes},t_in,F>=2], got {tuple(x.shape)}")
+    h, w = int(size[0]), int(size[1])
+    if h < 1 or w < 1 or scale < 1:
+        raise ValueError("size and scale must be positive")
+    M = index.shape[0]
+    dev = dets.device
+    flags = torch.zeros(M, 3, device=dev, dtype=torch.int32)
+    boxes = torch.zeros(M, 8, device=dev, dtype=torch.int32)
+    err = torch.zeros(M, 2, device=dev, dtype=torch.float64)
+    if M:
+        roi, x = _f(roi.detach()), _f(x.detach())
+        _lib.check(_lib.lib().c2m_match_detections(_p(_f(dets)), _p(_f(kept)), cap, N2 // 2, _p(_f(index)), M, _p(roi), roi.shape[1],
+                                                   _p(x), x.shape[1], x.shape[2], _p(_f(batch)), nodes, int(scale), h, w,
+                                                   0.005 * w * h, h * w * 0.01, _p(flags), _p(boxes), _p(err), _stream()),
+                   "match_detections")
+    return flags, boxes, err

@@ -403,6 +403,32 @@ int c2m_resize_flow(const float* src, float* dst, long N, int Hin, int Win, int 
                     const int32_t* bounds_x, const float* weight_x, int ksx, const int32_t* bounds_y_host,
                     const int32_t* bounds_y, const float* weight_y, int ksy, void* stream);
 
+/* The detector metric (c2m_amd.evaluate; reference: utils/utils_yolov3.py, yolo_v3/models.py YOLOLayer, yolo_v3/utils/utils.py
+ * non_max_suppression).  fp32, no atomics, every result bit-repeatable.
+ * c2m_detect_input: frame [B][C][H][W] through element strides (the last time index of a video is read in place) -> out
+ *   [B][C][S][S]: nearest x scale, zero to the right and below, cropped where the scaled frame is larger than S.
+ * c2m_yolo_candidates: heads[h] = device pointer to [N][na[h] * (5 + C)][grid[h]][grid[h]] raw head maps; HOST arrays grid, nanchors,
+ *   stride (image size / grid) and anchors [nheads][max_anchors][2] = (w, h) / stride.  Decodes every box, keeps conf >= conf_thres,
+ *   and writes them compacted in box order (head, anchor, row, column): cand [N][cap][7] = (x1, y1, x2, y2, conf, class_conf,
+ *   class), score [N][cap] = conf * class_conf (slots >= count[n] are not written), count [N].  cap >= boxes per image.
+ *   block_count: N * ceil(boxes / 256) ints of workspace.  Two launches (counts; prefix + scatter).
+ * c2m_nms_merge: sorted [N][cap][7] = the candidates by descending score; one workgroup per image runs the reference's loop:
+ *   head = first alive; invalid = alive, same class, IoU(head's original box, box) > nms_thres (+1 areas, 1e-16); output row =
+ *   head's row with box = sum conf * box / sum conf over invalid; invalid and the head are removed.  dets [N][cap][7], kept [N].
+ * c2m_match_detections: for object m: node index[m] of the graph (roi [nodes][T][4] = xmin, xmax, ymin, ymax and x
+ *   [nodes][tin][F], both read at the last time index; batch [nodes]); detections of image batch (ground truth) and B + batch
+ *   (predicted) of dets [2B][cap][7].  flags [M][3] = skipped (-1: index outside the graph), gt_found, pred_found; boxes [M][8] =
+ *   the two truncated boxes (y1, x1, y2, x2); err [M][2] = mse, mse_normalized.  skip_area = 0.005 w h, min_area = 0.01 h w.    */
+int c2m_detect_input(const float* frame, float* out, int B, int C, int H, int W, long stride_b, long stride_c, long stride_h,
+                     long stride_w, int scale, int S, void* stream);
+int c2m_yolo_candidates(const void* const* heads, const int* grid, const int* nanchors, const float* stride, const float* anchors,
+                        int max_anchors, int nheads, int N, int C, float conf_thres, int cap, int* block_count, float* cand,
+                        float* score, int* count, void* stream);
+int c2m_nms_merge(const float* sorted, const int* count, int N, int cap, float nms_thres, float* dets, int* kept, void* stream);
+int c2m_match_detections(const float* dets, const int* kept, int cap, int B, const long* index, int M, const float* roi, int T,
+                         const float* x, int tin, int F, const long* batch, long nodes, int scale, int h, int w,
+                         double skip_area, double min_area, int* flags, int* boxes, double* err, void* stream);
+
 /* Per-instance boxes of the input frames, for graphs built from instance maps instead of tracker files (click-to-move;
  * c2m_amd.interactive).  The reference has no counterpart: it reads per-object tracker boxes (cityscapes.py:79-199).
  * c2m_instance_stats: instance [B][T][H][W] int32, planes = (sample, input frame t < t_in); for every id in [id_lo, id_hi)
