@@ -842,24 +842,28 @@ class _ConvPlan:
         # ---- Winograd F(2x2,3x3) for the 3x3 stride-1 2-D layers (fp32 mode): forward, and the data gradient when the
         # padding is zeros (the reflect data gradient runs over the padded domain with the two-target epilogue)
         self.wino_fwd = self.wino_dgrad = self.wino_wgrad = self.ring_dgrad = False
-        self.wino4_fwd = self.wino4_dgrad = False         # F(4x4,3x3) instead of F(2x2,3x3) for that launch (2-D layers)
-        if not bf16 and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and (ph, pw) == (1, 1) and nd == 2:
+        # rows: 64-row tiles need >= 48 output channels to pay; 17..32 run on the 32-row variant (MT = 1, three
+        # workgroups per CU), which beats the direct kernels' 32-row tiles
+        rows_ok = lambda m: m >= 48 or 17 <= m <= 32
+
+        def wino_wgrad_pays(Kw, nimg):         # Winograd weight gradient over Kw input channels (3-D: virtual (kt, ci)) and nimg images
             wrows = 32 if Cout <= 32 else 64                      # workgroup tile: 64 (32 for Cout <= 32) output x 32 input channels
-            wg_tiles = _cdiv(Cin, 32) * _cdiv(Cout, wrows)
+            wg_tiles = _cdiv(Kw, 32) * _cdiv(Cout, wrows)
             # A/B against the direct kernel (tools/ab_wino_wgrad.py, AB_EXTRA=1 for the marginal shapes): the Winograd form
             # wins 1.1-1.3x even on a half-empty 64-row tile as long as there are two tiles
-            waste = 32.0 * wrows * wg_tiles / (Cin * Cout)
-            if Hi % 2 == 0 and Wi % 16 == 0 and (Cin * Cout) % 4 == 0 and (_WINO_WGRAD == "force" or (
+            waste = 32.0 * wrows * wg_tiles / (Kw * Cout)
+            if not (Hi % 2 == 0 and Wi % 16 == 0 and (Kw * Cout) % 4 == 0 and (_WINO_WGRAD == "force" or (
                     _WINO_WGRAD == "auto" and (waste <= 1.35 or (waste <= 2.0 and wg_tiles >= 2))
-                    and N * (Hi // 2) * (Wi // 16) >= 8 * max(1, (768 if wrows == 32 else 512) // wg_tiles))):
-                self.wino_wgrad = True
-                self.wino_wg_splits = L.c2m_wino_wgrad_splits(Cout, Cin, N, Hi, Wi)
+                    and nimg * (Hi // 2) * (Wi // 16) >= 8 * max(1, (768 if wrows == 32 else 512) // wg_tiles)))):
+                return False
+            self.wino_wg_splits = L.c2m_wino_wgrad_splits(Cout, Kw, nimg, Hi, Wi)
+            return True
+        self.wino4_fwd = self.wino4_dgrad = False         # F(4x4,3x3) instead of F(2x2,3x3) for that launch (2-D layers)
+        if not bf16 and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and (ph, pw) == (1, 1) and nd == 2:
+            self.wino_wgrad = wino_wgrad_pays(Cin, N)
             # regions per image: 8 x 16 outputs, or the th x tw tile shape c2m_conv_wino picks for a badly fitting domain
             regions = N * L.c2m_wino_regions(Ho, Wo)
             fit = N * Ho * Wo >= 0.8 * regions * 128
-            # rows: 64-row tiles need >= 48 output channels to pay; 17..32 run on the 32-row variant (MT = 1, three
-            # workgroups per CU), which beats the direct kernels' 32-row tiles
-            rows_ok = lambda m: m >= 48 or 17 <= m <= 32
             if _WINO == "force" or (_WINO == "auto" and fit and Cin >= 32 and rows_ok(Cout) and
                                     regions * _cdiv(Cout, 64) >= _WINO_MIN_WGS):
                 self.wino_fwd = True
@@ -871,7 +875,6 @@ class _ConvPlan:
             # by c2m_reflect_ring_dgrad (conv_ring.hip: four thin GEMMs, 3/9 (2H+2W)/(HW) of the layer's FLOPs -- maps of
             # >= _RING_MIN_PIX pixels), OR the padded (H+2)x(W+2) domain with the two-target epilogue (interior straight into dX,
             # pad ring into a scratch tensor that is then folded)
-            self.ring_dgrad = False
             if reflect and dM == Cin and _RING != "off" and Hi >= 4 and Wi >= 4 and (_RING == "force" or Hi * Wi >= _RING_MIN_PIX):
                 eregions = N * L.c2m_wino_regions(Hi, Wi)
                 efit = N * Hi * Wi >= 0.8 * eregions * 128
@@ -904,7 +907,6 @@ class _ConvPlan:
         # fold pass) or the unpadded one (zeros).
         self.wino3d = self.wino_wgrad3d = self.wino3d_pairs = False
         if not bf16 and nd == 3 and (kt, kh, kw) == (3, 3, 3) and tuple(stride) == (1, 1, 1) and (pt, ph, pw) == (1, 1, 1):
-            rows_ok = lambda m: m >= 48 or 17 <= m <= 32
             regions = N * To * L.c2m_wino_regions(Ho, Wo)
             fit = N * To * Ho * Wo >= 0.8 * regions * 128
             hw_i, hw_o = Hi * Wi, Ho * Wo
@@ -937,14 +939,7 @@ class _ConvPlan:
                     # straight into dX, only the pad ring into the scratch tensor; then the border-only fold)
                     self.wino_dgrad_geom[WG.Y2_SN:WG.EXT_X + 1] = (Cin * in_sc, in_sc, Wi, 1, 1, Hi, Wi)
             # weight gradient: the 2-D Winograd wgrad kernel over images (sample, frame) and virtual channels (kt, ci)
-            wrows = 32 if Cout <= 32 else 64
-            wg_tiles = _cdiv(3 * Cin, 32) * _cdiv(Cout, wrows)
-            waste = 32.0 * wrows * wg_tiles / (3 * Cin * Cout)
-            if Hi % 2 == 0 and Wi % 16 == 0 and (3 * Cin * Cout) % 4 == 0 and (_WINO_WGRAD == "force" or (
-                    _WINO_WGRAD == "auto" and (waste <= 1.35 or (waste <= 2.0 and wg_tiles >= 2))
-                    and N * Ti * (Hi // 2) * (Wi // 16) >= 8 * max(1, (768 if wrows == 32 else 512) // wg_tiles))):
-                self.wino_wgrad = self.wino_wgrad3d = True
-                self.wino_wg_splits = L.c2m_wino_wgrad_splits(Cout, 3 * Cin, N * Ti, Hi, Wi)
+            self.wino_wgrad = self.wino_wgrad3d = wino_wgrad_pays(3 * Cin, N * Ti)
         # ---- forward
         self.ck = ck = _choose_ck(Cin, taps)
         self.fwd_patch = False
@@ -1000,7 +995,7 @@ class _ConvPlan:
                               out_st=Ho * Wo, out_sh=Wo, out_sw=1, out_off=0, reflect=int(reflect), is3d=is3d, ns=ns,
                               in_sc=in_sc, splits=self.fwd_splits, slab_stride=N * Cout * osp,
                               x_bytes=4 * N * Cin * in_sc)
-        self.fwd_geom[[G.CIN, G.TAPS, G.NTG]] = (Cin, taps, ntg)
+        self.fwd_geom[[G.CIN, G.TAPS, G.NTG, G.PRECISION]] = (Cin, taps, ntg, int(bf16))      # (precision: read by c2m_conv_igemm / c2m_conv_wgrad)
         if kt == 1 and kh == kw and (st, sh, sw) == (1, 1, 1):
             self.fwd_geom[G.SQUARE_KW] = kw                # row-major square tap set, dx ascending (thin row-blocked kernel)
         if self.fwd_patch:
@@ -1073,7 +1068,7 @@ class _ConvPlan:
                                  in_sc=osp, splits=1, slab_stride=tgt_numel, x_bytes=4 * N * Cout * osp)
                     # two-target epilogue (reflect): padded coord = q*stride + r per dim; interior = [pad, pad + extent)
                     geom[G.PS_T:G.Y2_SH + 1] = (st, sh, sw, offt, offy, offx, pt, ph, pw, Ti, Hi, Wi, Cin * in_sc, in_sc, Hi * Wi, Wi)
-                    geom[[G.CIN, G.TAPS, G.NTG]] = (Cout, ctaps, cntg)
+                    geom[[G.CIN, G.TAPS, G.NTG, G.PRECISION]] = (Cout, ctaps, cntg, int(bf16))
                     if At == 1 and Ay == Ax and (st, sh, sw) == (1, 1, 1):
                         geom[G.SQUARE_KW] = -Ax            # data gradient: tap offsets run q - arange(A): dx descending
                     if cpatch:
@@ -1148,7 +1143,10 @@ class _ConvPlan:
             self.g8_fwd_splits = _g8_splits(Cout, taps * _cdiv(Cin, 16), N * osp)
             self.g8_fwd_geom = _g8_geom(self.fwd_geom, Cin, taps, self.g8_fwd_splits)
             self.g8_fwd_tab = _g8_taps(offs, device)
-        patch_nc8 = any(c["patch"] for c in cl) and not is3d and (Ho * Wo) % 8 == 0
+        # data gradient on the NC8 patch kernel: the single 3x3 stride-1 class of a bf16 layer whose dY planes are whole 8-pixel groups.
+        # (the ONE spelling; the three it replaces differed only in whether they tested bf16 / _NC8 themselves or sat behind a test of
+        # them -- `g8`, below, holds both, and patch classes are one class, so any() == all())
+        patch_nc8 = bool(bf16 and _NC8 and cl and all(c["patch"] for c in cl) and not is3d and (Ho * Wo) % 8 == 0)
         self.g8_dgrad = bool(g8 and cl and not (self.k333_dgrad_nc8 or self.s2_dgrad_nc8 or patch_nc8) and dM > 4 and chan_ok(Cout)
                              and osp % 8 == 0 and self.classes_packable and max(c["taps"] for c in cl) <= 64 and
                              not any(c["patch"] for c in cl))
@@ -1170,6 +1168,59 @@ class _ConvPlan:
                 grp["g8"] = _g8_geom(grp["geom"], Cout, ctaps, S8)
                 grp["g8"][G.A_CLS], grp["g8"][G.KTAB_CLS] = 0, 0
                 grp["g8tab"] = torch.cat([c["g8tab"] for c in cl[grp["first"]:grp["first"] + grp["ncls"]]])
+        # ---- routes: the kernel each pass of this layer runs on, by name (_ROUTE_PROF lists them).  The eligibility flags are read HERE
+        # only, in order of precedence (the NC8 flags hold `bf16` themselves, the Winograd ones `not bf16`); dispatch, the NC8-only
+        # predicates and the NC8 keep decisions read the names.  Knobs (_NC8, _G8, _WINO, ...) are fixed when the plan is built.
+        self.fwd_route = (("wino3d" if self.wino3d else "wino4" if self.wino4_fwd else "wino") if self.wino_fwd else
+                          "k333_nc8" if self.k333_nc8 else "s2_nc8" if self.s2_nc8 else "g8" if self.g8_fwd else
+                          "patch_nc8" if (self.fwd_patch and self.nc8) else "igemm")
+        self.dgrad_route = (("wino3d" if self.wino3d else ("wino4" if self.wino4_dgrad else "wino") + ("_ring" if self.ring_dgrad else ""))
+                            if self.wino_dgrad else
+                            "k333_nc8" if self.k333_dgrad_nc8 else "s2_nc8" if self.s2_dgrad_nc8 else "g8" if self.g8_dgrad else
+                            "igemm_batched" if self.cls_batch is not None else "patch_nc8" if patch_nc8 else "igemm")
+        self.wgrad_route = ("k333_nc8" if self.k333_wgrad_nc8 else "nc8" if self.wgrad_nc8 else "s2_nc8" if self.s2_wgrad_nc8 else
+                            "wino3d" if self.wino_wgrad3d else "wino" if self.wino_wgrad else "igemm")
+        # X in NC8 form goes from the forward launch to the weight gradient (ctx.nc8_keep); dY in NC8 form is shared by the two gradients
+        # of a backward node (`keep`).  keep_dy_nc8 is NOT the flag expression it replaces (bf16 and (nc8 or k333 wgrad / dgrad)): it
+        # also pins dY for g8 data gradients of 3-D layers and no longer makes an unused dict for 2-D layers without an NC8 route --
+        # the same layout passes either way (_to_nc8 also remembers its result on the tensor)
+        self.keep_x_nc8 = self.fwd_route in _NC8_KEEPS_X and self.wgrad_route in _NC8_WGRADS
+        self.keep_dy_nc8 = self.dgrad_route in _NC8_CONVS or self.wgrad_route in _NC8_WGRADS
+        # ---- what is the same for every call.  bf16 data path: bf16 in, bf16 out, except the <= 4-channel heads (flow, occlusion, RGB):
+        # fp32 out, and fp32 in on the vector-ALU kernels when the launch is big enough for them (_thin)
+        thin = bool(bf16 and _thin(Cout, self.fwd_splits, N * osp))
+        self.fwd_xdt = BF16 if (bf16 and not thin) else torch.float32
+        self.fwd_ydt = BF16 if (bf16 and not thin and Cout > 4) else torch.float32
+        self.in_shape = (N, Cin, Ti, Hi, Wi) if nd == 3 else (N, Cin, Hi, Wi)
+        S = self.dgrad_route_splits = self.g8_dgrad_splits if self.dgrad_route == "g8" else self.dgrad_splits
+        self.dgrad_folded = bool(reflect and any(pad))
+        self.dgrad_two_target = self.dgrad_folded and S == 1 and not self.dgrad_needs_zero
+        for c in cl:        # (a <= 4-channel input: such launches are fp32 in, fp32 out, and then the layer's target is fp32)
+            c["thin"] = bool(bf16 and self.cls_batch is None and _thin(dM, S, c["npix"], self.dgrad_two_target))
+
+        def prof(table, route, splits, *head):         # (profiler kind, tag) -- the data gradient's tag: its tail, per launch
+            kind, sfx = _ROUTE_PROF[table][route]
+            return kind + ("_bf16" if bf16 else ""), head + (self.dims[9:12], stride, reflect) + tuple(splits if v is None else v for v in sfx)
+        self.fwd_prof = prof("conv", self.fwd_route, self.g8_fwd_splits if self.g8_fwd else self.fwd_splits, "fwd", Cout, self.K, N * osp)
+        self.dgrad_prof = prof("conv", self.dgrad_route, S)
+        self.wgrad_prof = prof("wgrad", self.wgrad_route, self.wg_splits, "wgrad", Cout, self.K, N * osp)
+
+
+# route -> (profiler kind, tag suffix; None = the launch's split count): what bench.py (sums by kind) and the tools (read tag positions)
+# see of a route.  Launches of a bf16 plan are kind + "_bf16" (the NC8 routes exist in bf16 only, the Winograd ones in fp32 only).
+_ROUTE_PROF = {
+    "conv": {       # forward and data gradient (*_ring, igemm_batched: data gradient only)
+        "wino3d": ("wino", ("wino",)), "wino4": ("wino4", ("wino4",)), "wino": ("wino", ("wino",)),
+        "wino4_ring": ("wino4", ("wino4", "ring")), "wino_ring": ("wino", ("wino", "ring")),
+        "k333_nc8": ("igemm", ("nc8",)), "s2_nc8": ("igemm", ("nc8",)), "g8": ("igemm", (None, "nc8g")),
+        "patch_nc8": ("igemm", (None, "nc8")), "igemm_batched": ("igemm", (None,)), "igemm": ("igemm", (None,))},
+    "wgrad": {
+        "k333_nc8": ("wgrad", ("nc8",)), "nc8": ("wgrad", ("nc8",)), "s2_nc8": ("wgrad", ("nc8",)),
+        "wino3d": ("wino_wgrad", ("wino",)), "wino": ("wino_wgrad", ("wino",)), "igemm": ("wgrad", (None,))},
+}
+_NC8_CONVS = frozenset(("k333_nc8", "s2_nc8", "g8", "patch_nc8"))      # forward: reads X as NC8 only; data gradient: reads dY as NC8 only
+_NC8_KEEPS_X = _NC8_CONVS - {"g8"}                                      # ... and hands its NC8 X on (the gather form converts for itself)
+_NC8_WGRADS = frozenset(("k333_nc8", "nc8", "s2_nc8"))                  # weight gradient: reads X and dY as NC8 only
 
 
 def _bwd_reads_only_nc8(pl, need_x, need_w):
@@ -1177,13 +1228,7 @@ def _bwd_reads_only_nc8(pl, need_x, need_w):
     form): the gradient then need not exist in NCHW at all (`_virtual_grad`)."""
     if not (pl.bf16 and _NC8 and _NC8_GRAD and (pl.dims[6] * pl.dims[7] * pl.dims[8]) % 8 == 0):
         return False
-    if need_x:
-        patch_nc8 = bool(pl.classes) and all(c["patch"] for c in pl.classes) and not pl.is3d and (pl.dims[7] * pl.dims[8]) % 8 == 0
-        if not (pl.k333_dgrad_nc8 or pl.s2_dgrad_nc8 or pl.g8_dgrad or patch_nc8):
-            return False
-    if need_w and not (pl.k333_wgrad_nc8 or pl.wgrad_nc8 or pl.s2_wgrad_nc8):
-        return False
-    return True
+    return not (need_x and pl.dgrad_route not in _NC8_CONVS) and not (need_w and pl.wgrad_route not in _NC8_WGRADS)
 
 
 def _fwd_reads_only_nc8(pl, need_w):
@@ -1191,11 +1236,7 @@ def _fwd_reads_only_nc8(pl, need_w):
     reads the input): an activation whose single consumer is this layer need not exist in NCHW (`feeds=` of the norm ops)."""
     if not (pl.bf16 and _NC8 and _NC8_GRAD and (pl.dims[3] * pl.dims[4] * pl.dims[5]) % 8 == 0):
         return False
-    if not (pl.k333_nc8 or pl.s2_nc8 or (pl.fwd_patch and pl.nc8) or pl.g8_fwd):
-        return False
-    if need_w and not (pl.k333_wgrad_nc8 or pl.wgrad_nc8 or pl.s2_wgrad_nc8):
-        return False
-    return True
+    return pl.fwd_route in _NC8_CONVS and not (need_w and pl.wgrad_route not in _NC8_WGRADS)
 
 
 def _consumer_reads_only_nc8(like, feeds):
@@ -1220,17 +1261,6 @@ def conv_consumer(conv_w, stride=1, padding=0, padding_mode="zeros", conv_b=None
     return (conv_w, stride, padding, padding_mode, conv_b)
 
 
-def _tag_conv_output(ctx, pl, y, act):
-    """_ConvFn.forward: mark an output whose gradient this layer's backward will read through NC8 kernels only (no fused
-    activation: act_bwd reads the incoming gradient in NCHW).  A norm op told that it is the output's ONLY consumer
-    (`private_input=True`) then hands its dx back in NC8 form alone."""
-    if pl.bf16 and not ACT[act] and y.dtype == BF16:
-        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        if _bwd_reads_only_nc8(pl, ctx.needs_input_grad[0], need_w):
-            y._c2m_bwd_nc8 = True
-    return y
-
-
 def _virtual_grad(like, gn):
     """A gradient that exists in NC8 form only: a tensor object of the NCHW shape that carries `gn` for `_to_nc8` and whose own
     storage is never written or read (C2M_NC8_POISON=1 fills it with NaN -- the tests run the steps that way: a kernel that read
@@ -1241,19 +1271,17 @@ def _virtual_grad(like, gn):
     return _mark_nc8_only(g, gn)
 
 
-def _plan(x, w, stride, pad, reflect, dgrad_rows=None):
-    key = (tuple(x.shape), tuple(w.shape), stride, pad, reflect, x.device.index, _conv_bf16, dgrad_rows)
+def _plan_for(xs, ws, stride, pad, reflect, device, dgrad_rows=None):
+    """The cached plan of the convolution of an input of shape `xs` with a weight of shape `ws` in the current precision."""
+    key = (xs, ws, stride, pad, reflect, device.index, _conv_bf16, dgrad_rows)
     pl = _geom_cache.get(key)
     if pl is None:
-        pl = _geom_cache[key] = _ConvPlan(tuple(x.shape), tuple(w.shape), stride, pad, reflect, x.device, _conv_bf16,
-                                          dgrad_rows)
-        if _conv_bf16:                     # geom[34] = operand precision, read by c2m_conv_igemm / c2m_conv_wgrad
-            pl.fwd_geom[G.PRECISION] = pl.wg_geom[G.PRECISION] = 1
-            for c in pl.classes:
-                c["geom"][G.PRECISION] = 1
-            for grp in (pl.cls_batch["groups"] if pl.cls_batch else ()):
-                grp["geom"][G.PRECISION] = 1
+        pl = _geom_cache[key] = _ConvPlan(xs, ws, stride, pad, reflect, device, _conv_bf16, dgrad_rows)
     return pl
+
+
+def _plan(x, w, stride, pad, reflect, dgrad_rows=None):
+    return _plan_for(tuple(x.shape), tuple(w.shape), stride, pad, reflect, x.device, dgrad_rows)
 
 
 def _gp(a):
@@ -1395,218 +1423,358 @@ def _set_io(geom, x, ydt):
     return geom
 
 
-def _conv_dgrad(pl, w, gy, frozen_w, out_dtype=torch.float32, keep=None):
-    """Data gradient of the convolution described by plan `pl` (= the transposed convolution of gy with w): shared by
-    _ConvFn.backward and conv_transpose2d.  gy contiguous [N, Cout, (To,) Ho, Wo]; returns [N, Cin, (Ti,) Hi, Wi] in
-    `out_dtype` (the dtype of the forward input: bf16 on the bf16 data path, fp32 for fp32 inputs)."""
-    if not pl.bf16:
-        gy = _as(gy, torch.float32)
+def _dgrad_tag(pl, taps, npix):
+    """(kind, tag) of one data-gradient launch: `taps` weights per (input, output) channel pair over `npix` pixels."""
+    return pl.dgrad_prof[0], ("dgrad", pl.dims[1], pl.dims[2] * taps, npix) + pl.dgrad_prof[1]
+
+
+def _dgrad_wino3d(pl, w, gy, frozen_w, out_dtype, keep):
     L = _lib.lib()
     N, Cin, Cout = pl.dims[0:3]
-    Ti_, Hi_, Wi_ = pl.dims[3:6]
-    xshape = (N, Cin, Ti_, Hi_, Wi_) if pl.is3d else (N, Cin, Hi_, Wi_)
-    xnumel = N * Cin * Ti_ * Hi_ * Wi_
-    dev = gy.device
-    gx = None
-    if pl.wino_dgrad and pl.wino3d:
-        dM = pl.dM
-        # virtual channels (flipped time tap, output channel): a "native" [3*Cout][dM][3][3] weight for the 2-D transform
-        U = _packed(w, frozen_w, ("wino-dgrad3d", dM), lambda: _wino_filter(
-            w[:, :dM].flip(2).permute(2, 0, 1, 3, 4).reshape(3 * Cout, dM, 3, 3).contiguous(), 3 * Cout, dM, 1))
-        gx = torch.empty(xshape, device=dev, dtype=torch.float32)
-        tgt = torch.empty(pl.wino_dgrad_target, device=dev, dtype=torch.float32) if pl.reflect else gx
-        g3 = pl.wino_dgrad_geom
-        npix = int(g3[WG.NIMG] * g3[WG.HO] * g3[WG.WO])
-        tag = ("dgrad", Cin, Cout * 27, npix, pl.dims[9:12], pl.stride, pl.reflect, "wino")
-        two = pl.reflect and pl.wino3d_pairs
-        _lib.check(_timed("wino", pl.dgrad_flops,
-                          lambda: L.c2m_conv_wino(_p(U), _p(gy), _p(tgt), _p(gx) if two else None, None, _gp(g3), 0, 0.0,
-                                                  _stream()), tag,
-                          4 * (gy.numel() + w.numel() + xnumel)), "conv_wino dgrad 3-D")
-        if pl.reflect:
-            Ti, Hi, Wi = pl.dims[3:6]
-            if two:
-                _lib.check(L.c2m_reflect_border_add(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 0, 1, 1, 0, _stream()),
-                           "reflect border add 3-D")
-            else:
-                _lib.check(L.c2m_reflect_fold(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 1, 1, 1, 0, _stream()), "reflect fold 3-D")
-        if dM < Cin:
-            gx[:, dM:].zero_()
-    elif pl.wino_dgrad:
-        w4 = pl.wino4_dgrad
-        U = _packed(w, frozen_w, ("wino4-dgrad",), lambda: _wino4_filter(w, Cout, Cin, 1)) if w4 else \
-            _packed(w, frozen_w, ("wino-dgrad",), lambda: _wino_filter(w, Cout, Cin, 1))
-        conv_wino = L.c2m_conv_wino4 if w4 else L.c2m_conv_wino
-        gx = torch.empty(xshape, device=dev, dtype=torch.float32)
-        npix = int(pl.wino_dgrad_geom[WG.NIMG] * pl.wino_dgrad_geom[WG.HO] * pl.wino_dgrad_geom[WG.WO])
-        tag = ("dgrad", Cin, Cout * 9, npix, pl.dims[9:12], pl.stride, pl.reflect, "wino4" if w4 else "wino")
-        if pl.ring_dgrad:
-            # reflect, exact domain: the interior term straight into gx, then the pad ring added in place (conv_ring.hip) -- both
-            # launches inside the timed region of this layer's data gradient
-            Ar = _packed(w, frozen_w, ("ring-dgrad",), lambda: _ring_pack(w, Cout, Cin))
-            Hi_, Wi_ = pl.dims[4:6]
-            g_ = pl.wino_dgrad_geom
-            if _RING_BUFFER:
-                # buffer form: the ring launch WRITES its terms (coalesced, no read-modify-write of dX, no corner part) and the
-                # Winograd launch behind it adds them in its epilogue
-                r_l = _ceil(max(Hi_, Wi_), 4)
-                R = torch.empty(N * Cin * 4 * r_l, device=dev, dtype=torch.float32)
+    Ti, Hi, Wi = pl.dims[3:6]
+    dM = pl.dM
+    # virtual channels (flipped time tap, output channel): a "native" [3*Cout][dM][3][3] weight for the 2-D transform
+    U = _packed(w, frozen_w, ("wino-dgrad3d", dM), lambda: _wino_filter(
+        w[:, :dM].flip(2).permute(2, 0, 1, 3, 4).reshape(3 * Cout, dM, 3, 3).contiguous(), 3 * Cout, dM, 1))
+    gx = torch.empty(pl.in_shape, device=gy.device, dtype=torch.float32)
+    tgt = torch.empty(pl.wino_dgrad_target, device=gy.device, dtype=torch.float32) if pl.reflect else gx
+    g3 = pl.wino_dgrad_geom
+    two = pl.reflect and pl.wino3d_pairs
+    kind, tag = _dgrad_tag(pl, 27, int(g3[WG.NIMG] * g3[WG.HO] * g3[WG.WO]))
+    _lib.check(_timed(kind, pl.dgrad_flops,
+                      lambda: L.c2m_conv_wino(_p(U), _p(gy), _p(tgt), _p(gx) if two else None, None, _gp(g3), 0, 0.0, _stream()), tag,
+                      4 * (gy.numel() + w.numel() + gx.numel())), "conv_wino dgrad 3-D")
+    if pl.reflect:
+        if two:
+            _lib.check(L.c2m_reflect_border_add(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 0, 1, 1, 0, _stream()), "reflect border add 3-D")
+        else:
+            _lib.check(L.c2m_reflect_fold(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 1, 1, 1, 0, _stream()), "reflect fold 3-D")
+    return gx
 
-                def run_ring():
-                    rc = L.c2m_reflect_ring_buffer(_p(Ar), _p(gy), _p(R), N, Cout, Cin, Hi_, Wi_, r_l, _stream())
-                    g_[WG.RING], g_[WG.RING_L] = R.data_ptr(), r_l
-                    try:
-                        return rc or conv_wino(_p(U), _p(gy), _p(gx), None, None, _gp(g_), 0, 0.0, _stream())
-                    finally:
-                        g_[WG.RING], g_[WG.RING_L] = 0, 0
-            else:
-                def run_ring():
-                    rc = conv_wino(_p(U), _p(gy), _p(gx), None, None, _gp(g_), 0, 0.0, _stream())
-                    return rc or L.c2m_reflect_ring_dgrad(_p(Ar), _p(w), _p(gy), _p(gx), N, Cout, Cin, Hi_, Wi_, _stream())
-            _lib.check(_timed("wino4" if w4 else "wino", pl.fwd_flops, run_ring, tag + ("ring",),
-                              4 * (gy.numel() + w.numel() + xnumel)), "conv_wino dgrad + reflect ring")
-            return gx if gx.dtype == out_dtype else gx.to(out_dtype)
-        # reflect: ring of the padded domain -> tgt (only the ring is ever written or read), interior -> gx
-        tgt = torch.empty(pl.dgrad_target, device=dev, dtype=torch.float32) if pl.reflect else gx
-        _lib.check(_timed("wino4" if w4 else "wino", pl.fwd_flops,
-                          lambda: conv_wino(_p(U), _p(gy), _p(tgt), _p(gx) if pl.reflect else None, None,
-                                            _gp(pl.wino_dgrad_geom), 0, 0.0, _stream()), tag,
-                          4 * (gy.numel() + w.numel() + xnumel)), "conv_wino dgrad")
-        if pl.reflect:
-            Ti, Hi, Wi = pl.dims[3:6]
-            _lib.check(L.c2m_reflect_border_add(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 0, 1, 1, 0, _stream()),
-                       "reflect border add")
-    elif pl.bf16 and pl.k333_dgrad_nc8:
-        # 3x3x3 layers: (sample, frame) images, frame t summing its (dY frame, time tap) pairs; reflect: spatially padded target + fold
-        gy_b = _as(gy, BF16)
-        kdt = BF16 if out_dtype == BF16 else torch.float32
+
+def _dgrad_wino(pl, w, gy, frozen_w, out_dtype, keep):
+    """Routes wino / wino4 (zeros: the unpadded domain; reflect: the padded domain with the two-target epilogue) and wino_ring /
+    wino4_ring (reflect: the exact domain + the pad ring, conv_ring.hip)."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    Ti, Hi, Wi = pl.dims[3:6]
+    dev = gy.device
+    g_ = pl.wino_dgrad_geom
+    if pl.dgrad_route in ("wino4", "wino4_ring"):
+        U, conv_wino = _packed(w, frozen_w, ("wino4-dgrad",), lambda: _wino4_filter(w, Cout, Cin, 1)), L.c2m_conv_wino4
+    else:
+        U, conv_wino = _packed(w, frozen_w, ("wino-dgrad",), lambda: _wino_filter(w, Cout, Cin, 1)), L.c2m_conv_wino
+    gx = torch.empty(pl.in_shape, device=dev, dtype=torch.float32)
+    kind, tag = _dgrad_tag(pl, 9, int(g_[WG.NIMG] * g_[WG.HO] * g_[WG.WO]))
+    nbytes = 4 * (gy.numel() + w.numel() + gx.numel())
+    if pl.dgrad_route in ("wino_ring", "wino4_ring"):
+        # the interior term straight into gx, then the pad ring added in place -- both launches inside the timed region of this
+        # layer's data gradient
+        Ar = _packed(w, frozen_w, ("ring-dgrad",), lambda: _ring_pack(w, Cout, Cin))
+        if _RING_BUFFER:
+            # buffer form: the ring launch WRITES its terms (coalesced, no read-modify-write of dX, no corner part) and the
+            # Winograd launch behind it adds them in its epilogue
+            r_l = _ceil(max(Hi, Wi), 4)
+            R = torch.empty(N * Cin * 4 * r_l, device=dev, dtype=torch.float32)
+
+            def run_ring():
+                rc = L.c2m_reflect_ring_buffer(_p(Ar), _p(gy), _p(R), N, Cout, Cin, Hi, Wi, r_l, _stream())
+                g_[WG.RING], g_[WG.RING_L] = R.data_ptr(), r_l
+                try:
+                    return rc or conv_wino(_p(U), _p(gy), _p(gx), None, None, _gp(g_), 0, 0.0, _stream())
+                finally:
+                    g_[WG.RING], g_[WG.RING_L] = 0, 0
+        else:
+            def run_ring():
+                rc = conv_wino(_p(U), _p(gy), _p(gx), None, None, _gp(g_), 0, 0.0, _stream())
+                return rc or L.c2m_reflect_ring_dgrad(_p(Ar), _p(w), _p(gy), _p(gx), N, Cout, Cin, Hi, Wi, _stream())
+        _lib.check(_timed(kind, pl.fwd_flops, run_ring, tag, nbytes), "conv_wino dgrad + reflect ring")
+        return gx
+    # reflect: ring of the padded domain -> tgt (only the ring is ever written or read), interior -> gx
+    tgt = torch.empty(pl.dgrad_target, device=dev, dtype=torch.float32) if pl.reflect else gx
+    _lib.check(_timed(kind, pl.fwd_flops,
+                      lambda: conv_wino(_p(U), _p(gy), _p(tgt), _p(gx) if pl.reflect else None, None, _gp(g_), 0, 0.0, _stream()), tag,
+                      nbytes), "conv_wino dgrad")
+    if pl.reflect:
+        _lib.check(L.c2m_reflect_border_add(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 0, 1, 1, 0, _stream()), "reflect border add")
+    return gx
+
+
+def _dgrad_nc8(pl, w, gy, frozen_w, out_dtype, keep):
+    """Routes k333_nc8 (3x3x3 layers: (sample, frame) images, frame t summing its (dY frame, time tap) pairs) and s2_nc8 (4x4 stride-2
+    layers: all four output parity classes in one launch) on the NC8 form of dY (conv_nc8.hip); reflect: spatially padded target + fold."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    Ti, Hi, Wi = pl.dims[3:6]
+    gy_b = _as(gy, BF16)
+    kdt = BF16 if out_dtype == BF16 else torch.float32
+    gx = torch.empty(pl.in_shape, device=gy.device, dtype=kdt)
+    if pl.dgrad_route == "k333_nc8":
         dM = pl.dM
         A = _packed(w, frozen_w, ("dgrad-bf16-k333", dM), lambda: _pack_bf16_k333(w, dM, Cout, dgrad=True, cin_total=Cin))
-        gx = torch.empty(xshape, device=dev, dtype=kdt)
-        tgt = torch.empty((N, Cin, Ti_, Hi_ + 2, Wi_ + 2), device=dev, dtype=kdt) if pl.reflect else gx
-        tag = ("dgrad", Cin, Cout * 27, int(N * Ti_ * Hi_ * Wi_), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
+        tgt = torch.empty((N, Cin, Ti, Hi + 2, Wi + 2), device=gy.device, dtype=kdt) if pl.reflect else gx
+        taps, what = 27, "conv3d_dgrad_nc8"
 
-        def run_k333d():
+        def run():
             gyn = _to_nc8(gy_b, keep)
-            return L.c2m_conv3d_dgrad_nc8(_p(A), _p(gyn), _p(tgt), _p(pl.k333_ptab), dM, Cin, Cout, N, Ti_, Hi_, Wi_, int(pl.reflect),
+            return L.c2m_conv3d_dgrad_nc8(_p(A), _p(gyn), _p(tgt), _p(pl.k333_ptab), dM, Cin, Cout, N, Ti, Hi, Wi, int(pl.reflect),
                                           _dt(tgt), _stream())
-        _lib.check(_timed("igemm_bf16", pl.dgrad_flops, run_k333d, tag, 2 * (gy.numel() + xnumel) + 4 * w.numel()), "conv3d_dgrad_nc8")
-        if pl.reflect:
-            _lib.check(L.c2m_reflect_fold(_p(tgt), _p(gx), N * Cin, Ti_, Hi_, Wi_, 0, 1, 1, _dt(tgt), _stream()), "reflect fold (3-D, spatial)")
-        if dM < Cin:
-            gx[:, dM:].zero_()               # channels declared gradient-free by the caller (dgrad_channels); their planes of tgt were never written
-    elif pl.bf16 and pl.s2_dgrad_nc8:
-        # 4x4 stride-2 layers: all four output parity classes in one launch on the NC8 form of dY (conv_nc8.hip)
-        gy_b = _as(gy, BF16)
-        Ho_, Wo_ = pl.dims[7:9]
-        kdt = BF16 if out_dtype == BF16 else torch.float32
-        A = _packed(w, frozen_w, ("dgrad-bf16-s2", pl.reflect), lambda: _pack_bf16_patch(w, Cin, Cout, 16, Cin * 16, 4 if pl.reflect else 3))
-        gx = torch.empty(xshape, device=dev, dtype=kdt)
-        tgt = torch.empty(pl.dgrad_target, device=dev, dtype=kdt) if pl.reflect else gx
-        tag = ("dgrad", Cin, Cout * 16, int(N * Hi_ * Wi_), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
-
-        def run_s2d():
-            gyn = _to_nc8(gy_b, keep)
-            return L.c2m_conv_s2_dgrad_nc8(_p(A), _p(gyn), _p(tgt), Cin, Cout, N, Ho_, Wo_, int(pl.reflect), _dt(tgt), _stream())
-        _lib.check(_timed("igemm_bf16", pl.dgrad_flops, run_s2d, tag, 2 * (gy.numel() + xnumel) + 4 * w.numel()), "conv_s2_dgrad_nc8")
-        if pl.reflect:
-            _lib.check(L.c2m_reflect_fold(_p(tgt), _p(gx), N * Cin, 1, Hi_, Wi_, 0, 1, 1, _dt(tgt), _stream()), "reflect fold (s2)")
     else:
-        g8 = pl.bf16 and pl.g8_dgrad                 # the NC8 gather form of the same launches (conv_gather_nc8_kernel)
-        S = pl.g8_dgrad_splits if g8 else pl.dgrad_splits
-        folded = pl.reflect and any(pl.pad)
-        two_target = folded and S == 1 and not pl.dgrad_needs_zero
-        alloc = torch.zeros if pl.dgrad_needs_zero else torch.empty
-        cb = pl.cls_batch
-        # bf16 data path: the bf16 kernels gather gy as bf16 and write `kdt`; the <= 4-row vector-ALU kernels (dgrad of a
-        # <= 4-channel input) are fp32 in, fp32 out -- if any launch of this layer is one of those, the layer's target is fp32
-        gy_b = gy_f = None
-        thin_of = {}
-        kdt = torch.float32
-        if pl.bf16:
-            if cb is None:
-                thin_of = {id(c): _thin(pl.dM, S, c["npix"], two_target, 1) for c in pl.classes}
-            any_thin = any(thin_of.values())
-            kdt = BF16 if (out_dtype == BF16 and not any_thin) else torch.float32
-            if cb is not None or not all(thin_of.values()):
-                gy_b = _as(gy, BF16)
-            if any_thin:
-                gy_f = _as(gy, torch.float32)
-        tgt = alloc(pl.dgrad_target, device=dev, dtype=kdt)
-        gx = torch.empty(xshape, device=dev, dtype=kdt) if folded else tgt.view(xshape)
-        dst = tgt if S == 1 else alloc(S * tgt.numel(), device=dev, dtype=torch.float32)
+        Ho, Wo = pl.dims[7:9]
+        A = _packed(w, frozen_w, ("dgrad-bf16-s2", pl.reflect), lambda: _pack_bf16_patch(w, Cin, Cout, 16, Cin * 16, 4 if pl.reflect else 3))
+        tgt = torch.empty(pl.dgrad_target, device=gy.device, dtype=kdt) if pl.reflect else gx
+        taps, what = 16, "conv_s2_dgrad_nc8"
+
+        def run():
+            gyn = _to_nc8(gy_b, keep)
+            return L.c2m_conv_s2_dgrad_nc8(_p(A), _p(gyn), _p(tgt), Cin, Cout, N, Ho, Wo, int(pl.reflect), _dt(tgt), _stream())
+    kind, tag = _dgrad_tag(pl, taps, int(N * Ti * Hi * Wi))
+    _lib.check(_timed(kind, pl.dgrad_flops, run, tag, 2 * (gy.numel() + gx.numel()) + 4 * w.numel()), what)
+    if pl.reflect:
+        _lib.check(L.c2m_reflect_fold(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, 0, 1, 1, _dt(tgt), _stream()), "reflect fold (NC8, spatial)")
+    return gx
+
+
+def _dgrad_igemm(pl, w, gy, frozen_w, out_dtype, keep):
+    """Routes igemm and patch_nc8 (one c2m_conv_igemm / c2m_conv_patch_nc8 launch per stride-parity class), igemm_batched (one per
+    group of classes) and g8 (either, on the NC8 gather form): shared target, split-K slabs, reduction and reflect fold."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    route, S, two_target, cb = pl.dgrad_route, pl.dgrad_route_splits, pl.dgrad_two_target, pl.cls_batch
+    alloc = torch.zeros if pl.dgrad_needs_zero else torch.empty
+    dev = gy.device
+    # bf16 data path: the bf16 kernels gather gy as bf16 and write `kdt`; the <= 4-row vector-ALU kernels (c["thin"]) are fp32 in,
+    # fp32 out -- if any launch of this layer is one of those, the layer's target is fp32
+    gy_b = gy_f = None
+    kdt = torch.float32
+    if pl.bf16:
+        thin = [c["thin"] for c in pl.classes]
+        kdt = BF16 if (out_dtype == BF16 and not any(thin)) else torch.float32
+        if not all(thin):
+            gy_b = _as(gy, BF16)
+        if any(thin):
+            gy_f = _as(gy, torch.float32)
+    tgt = alloc(pl.dgrad_target, device=dev, dtype=kdt)
+    gx = torch.empty(pl.in_shape, device=dev, dtype=kdt) if pl.dgrad_folded else tgt.view(pl.in_shape)
+    gx2 = gx if two_target else None
+    dst = tgt if S == 1 else alloc(S * tgt.numel(), device=dev, dtype=torch.float32)
+    xnumel = gx.numel()
+    kdims = kt, kh, kw = pl.dims[9:12]
+    pack_all = (Cout, kdims, pl.stride, kt * kh * kw, Cin * kt * kh * kw)        # (every class image of the weights in one pack)
+    kind = pl.dgrad_prof[0]
+    if route == "g8":
+        A8 = _packed(w, frozen_w, ("dgrad-bf16-g8", pl.dM, pl.stride), lambda: _pack_bf16_gather(w, pl.dM, *pack_all))
+        launches = [(grp["g8"], grp["g8tab"], grp["first"], cb["taps"] * grp["npix"] * grp["ncls"], grp["npix"] * grp["ncls"])
+                    for grp in cb["groups"]] if cb is not None else \
+                   [(c["g8"], c["g8tab"], ci, c["taps"] * c["npix"], c["npix"]) for ci, c in enumerate(pl.classes)]
+        for geom8, tab8, first, work, npix in launches:
+            Ag = A8[first * pl.g8_a_cls:]
+
+            def run_g8d():
+                gyn = _to_nc8(gy_b, keep)
+                _set_io(geom8, gyn, kdt)
+                return L.c2m_conv_igemm(_p(Ag), _p(gyn), _p(dst), _p(gx2), None, _p(tab8), _gp(geom8), 0, 0.0, _stream())
+            _lib.check(_timed(kind, pl.dgrad_flops * work / pl.dgrad_work, run_g8d, _dgrad_tag(pl, pl.classes[0]["taps"], npix)[1],
+                              (2 * (gy.numel() + xnumel) + 4 * w.numel()) * work // int(pl.dgrad_work)),
+                       "conv_igemm dgrad (NC8 gather)")
+    elif route == "igemm_batched":
+        A = _packed(w, frozen_w, ("dgrad-all", cb["ck"], pl.stride), lambda: _pack_native(w, Cin, Cout, cb["ck"], *pack_all[1:]))
+        gin = gy_b if pl.bf16 else gy
+        for grp in cb["groups"]:
+            Ag = A[grp["first"] * Cin:]
+            _set_io(grp["geom"], gin, kdt)
+            _lib.check(_timed(kind, pl.dgrad_flops * cb["taps"] * grp["npix"] * grp["ncls"] / pl.dgrad_work,
+                              lambda: L.c2m_conv_igemm(_p(Ag), _p(gin), _p(dst), _p(gx2), None, _p(grp["tab"]), _gp(grp["geom"]), 0, 0.0,
+                                                       _stream()), _dgrad_tag(pl, cb["taps"], grp["npix"] * grp["ncls"])[1],
+                              4 * (gy.numel() * grp["ncls"] // cb["ncls"] + w.numel() + xnumel * grp["ncls"] // cb["ncls"])),
+                       "conv_igemm dgrad (batched classes)")
+    else:
         st, sh, sw = pl.stride
         w5 = w if pl.is3d else w.unsqueeze(2)
-        if g8:
-            kt, kh, kw = pl.dims[9:12]
-            A8 = _packed(w, frozen_w, ("dgrad-bf16-g8", pl.dM, pl.stride), lambda: _pack_bf16_gather(
-                w, pl.dM, Cout, (kt, kh, kw), pl.stride, kt * kh * kw, Cin * kt * kh * kw))
-            launches = [(grp["g8"], grp["g8tab"], grp["first"], cb["taps"] * grp["npix"] * grp["ncls"], grp["npix"] * grp["ncls"])
-                        for grp in cb["groups"]] if cb is not None else \
-                       [(c["g8"], c["g8tab"], ci, c["taps"] * c["npix"], c["npix"]) for ci, c in enumerate(pl.classes)]
-            for geom8, tab8, first, work, npix in launches:
-                tag = ("dgrad", Cin, Cout * pl.classes[0]["taps"], npix, pl.dims[9:12], pl.stride, pl.reflect, S, "nc8g")
-                Ag = A8[first * pl.g8_a_cls:]
-
-                def run_g8d():
-                    gyn = _to_nc8(gy_b, keep)
-                    _set_io(geom8, gyn, kdt)
-                    return L.c2m_conv_igemm(_p(Ag), _p(gyn), _p(dst), _p(gx) if two_target else None, None, _p(tab8), _gp(geom8),
-                                            0, 0.0, _stream())
-                _lib.check(_timed("igemm_bf16", pl.dgrad_flops * work / pl.dgrad_work, run_g8d, tag,
-                                  (2 * (gy.numel() + xnumel) + 4 * w.numel()) * work // int(pl.dgrad_work)),
-                           "conv_igemm dgrad (NC8 gather)")
-        elif cb is not None:
-            kt, kh, kw = pl.dims[9:12]
-            A = _packed(w, frozen_w, ("dgrad-all", cb["ck"], pl.stride), lambda: _pack_native(
-                w, Cin, Cout, cb["ck"], (kt, kh, kw), pl.stride, kt * kh * kw, Cin * kt * kh * kw))
-            for grp in cb["groups"]:
-                Ag = A[grp["first"] * Cin:]
-                tag = ("dgrad", Cin, Cout * cb["taps"], grp["npix"] * grp["ncls"], pl.dims[9:12], pl.stride,
-                       pl.reflect, S)
-                gin = gy_b if pl.bf16 else gy
-                _set_io(grp["geom"], gin, kdt)
-                _lib.check(_timed("igemm_bf16" if pl.bf16 else "igemm",
-                                  pl.dgrad_flops * cb["taps"] * grp["npix"] * grp["ncls"] / pl.dgrad_work,
-                                  lambda: L.c2m_conv_igemm(_p(Ag), _p(gin), _p(dst), _p(gx) if two_target else None,
-                                                           None, _p(grp["tab"]), _gp(grp["geom"]), 0, 0.0,
-                                                           _stream()), tag,
-                                  4 * (gy.numel() * grp["ncls"] // cb["ncls"] + w.numel() +
-                                       xnumel * grp["ncls"] // cb["ncls"])),
-                           "conv_igemm dgrad (batched classes)")
-        kt, kh, kw = pl.dims[9:12]
         Aall = None
-        if cb is None and not g8 and pl.classes_packable and not (pl.bf16 and all(c["patch"] for c in pl.classes)):
+        if pl.classes_packable and not (pl.bf16 and all(c["patch"] for c in pl.classes)):
             Aall = _packed(w, frozen_w, ("dgrad-all", pl.classes[0]["ck"], pl.stride), lambda: _pack_native(
-                w, Cin, Cout, pl.classes[0]["ck"], (kt, kh, kw), pl.stride, kt * kh * kw, Cin * kt * kh * kw))
-        for ci, c in enumerate(pl.classes if (cb is None and not g8) else ()):
+                w, Cin, Cout, pl.classes[0]["ck"], *pack_all[1:]))
+        for ci, c in enumerate(pl.classes):
             rt, ry, rx = c["r"]
             A = _packed(w, frozen_w, ("dgrad-bf16-patch", pl.dM), lambda: _pack_bf16_patch(
                 w, pl.dM, Cout, 9, Cin * 9)) if (c["patch"] and pl.bf16) else \
                 Aall[ci * Cin:] if Aall is not None else _packed(
                 w, frozen_w, ("dgrad", c["ck"], pl.stride, c["r"]), lambda: _pack_rows(
                     w5[:, :, rt::st, ry::sh, rx::sw].reshape(Cout, Cin, c["taps"]).transpose(0, 1), c["ck"]))
-            tag = ("dgrad", Cin, Cout * c["taps"], c["npix"], pl.dims[9:12], pl.stride, pl.reflect, S)
-            gin = (gy_f if thin_of.get(id(c)) else gy_b) if pl.bf16 else gy
-            _set_io(c["geom"], gin, torch.float32 if thin_of.get(id(c)) else kdt)
-            nc8 = c["patch"] and pl.bf16 and _NC8 and not pl.is3d and (pl.dims[7] * pl.dims[8]) % 8 == 0
-            _lib.check(_timed("igemm_bf16" if pl.bf16 else "igemm", pl.dgrad_flops * c["taps"] * c["npix"] / pl.dgrad_work,
-                              (lambda: _nc8_launch(L, A, gin, dst, gx if two_target else None, None, c["geom"], 0, 0.0, keep)) if nc8 else
-                              (lambda: L.c2m_conv_igemm(_p(A), _p(gin), _p(dst), _p(gx) if two_target else None, None,
-                                                        _p(c["tab"]), _gp(c["geom"]), 0, 0.0, _stream())),
-                              tag + (("nc8",) if nc8 else ()),
+            gin = (gy_f if c["thin"] else gy_b) if pl.bf16 else gy
+            _set_io(c["geom"], gin, torch.float32 if c["thin"] else kdt)
+            _lib.check(_timed(kind, pl.dgrad_flops * c["taps"] * c["npix"] / pl.dgrad_work,
+                              (lambda: _nc8_launch(L, A, gin, dst, gx2, None, c["geom"], 0, 0.0, keep)) if route == "patch_nc8" else
+                              (lambda: L.c2m_conv_igemm(_p(A), _p(gin), _p(dst), _p(gx2), None, _p(c["tab"]), _gp(c["geom"]), 0, 0.0,
+                                                        _stream())), _dgrad_tag(pl, c["taps"], c["npix"])[1],
                               4 * (gy.numel() + w.numel() + xnumel) // len(pl.classes)), "conv_igemm dgrad")
-        if S > 1:
-            _lib.check(L.c2m_splitk_reduce(_p(dst), _p(tgt), None, tgt.numel(), S, 1, 1, 0, 0.0, _dt(tgt), _stream()),
-                       "splitk_reduce dgrad")
-        if folded:
-            Ti, Hi, Wi = pl.dims[3:6]
-            fold = L.c2m_reflect_border_add if two_target else L.c2m_reflect_fold
-            _lib.check(fold(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, pl.pad[0], pl.pad[1], pl.pad[2], _dt(tgt), _stream()),
-                       "reflect fold")
-        if pl.dM < Cin:
-            gx[:, pl.dM:].zero_()            # channels declared gradient-free by the caller (dgrad_rows)
+    if S > 1:
+        _lib.check(L.c2m_splitk_reduce(_p(dst), _p(tgt), None, tgt.numel(), S, 1, 1, 0, 0.0, _dt(tgt), _stream()),
+                   "splitk_reduce dgrad")
+    if pl.dgrad_folded:
+        Ti, Hi, Wi = pl.dims[3:6]
+        fold = L.c2m_reflect_border_add if two_target else L.c2m_reflect_fold
+        _lib.check(fold(_p(tgt), _p(gx), N * Cin, Ti, Hi, Wi, pl.pad[0], pl.pad[1], pl.pad[2], _dt(tgt), _stream()),
+                   "reflect fold")
+    return gx
+
+
+_DGRAD = {"wino3d": _dgrad_wino3d, "wino4": _dgrad_wino, "wino": _dgrad_wino, "wino4_ring": _dgrad_wino, "wino_ring": _dgrad_wino,
+          "k333_nc8": _dgrad_nc8, "s2_nc8": _dgrad_nc8, "g8": _dgrad_igemm, "igemm_batched": _dgrad_igemm, "patch_nc8": _dgrad_igemm,
+          "igemm": _dgrad_igemm}
+
+
+def _conv_dgrad(pl, w, gy, frozen_w, out_dtype=torch.float32, keep=None):
+    """Data gradient of the convolution described by plan `pl` (= the transposed convolution of gy with w): shared by
+    _ConvFn.backward and conv_transpose2d.  gy contiguous [N, Cout, (To,) Ho, Wo]; returns [N, Cin, (Ti,) Hi, Wi] in
+    `out_dtype` (the dtype of the forward input: bf16 on the bf16 data path, fp32 for fp32 inputs)."""
+    if not pl.bf16:
+        gy = _as(gy, torch.float32)
+    gx = _DGRAD[pl.dgrad_route](pl, w, gy, frozen_w, out_dtype, keep)
+    if pl.dM < pl.dims[1]:
+        gx[:, pl.dM:].zero_()            # channels declared gradient-free by the caller (dgrad_rows); their planes were never written
     return gx if gx.dtype == out_dtype else gx.to(out_dtype)
+
+
+def _fwd_timed(pl, run, x, w, y, what):
+    _lib.check(_timed(pl.fwd_prof[0], pl.fwd_flops, run, pl.fwd_prof[1],
+                      x.element_size() * x.numel() + 4 * w.numel() + y.element_size() * y.numel()), what)
+
+
+def _fwd_wino(pl, x, w, b, y, act, slope, frozen_w, keep):
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    conv_wino = L.c2m_conv_wino
+    if pl.fwd_route == "wino3d":      # virtual channels (kt, ci): [Cout][3*Cin][3][3]
+        U = _packed(w, frozen_w, ("wino-fwd3d",), lambda: _wino_filter(
+            w.permute(0, 2, 1, 3, 4).reshape(Cout, 3 * Cin, 3, 3).contiguous(), Cout, 3 * Cin, 0))
+    elif pl.fwd_route == "wino4":     # F(4x4,3x3): its own roofline family (executed = algorithmic / 4)
+        U, conv_wino = _packed(w, frozen_w, ("wino4-fwd",), lambda: _wino4_filter(w, Cout, Cin, 0)), L.c2m_conv_wino4
+    else:
+        U = _packed(w, frozen_w, ("wino-fwd",), lambda: _wino_filter(w, Cout, Cin, 0))
+    _fwd_timed(pl, lambda: conv_wino(_p(U), _p(x), _p(y), None, _p(b), _gp(pl.wino_fwd_geom), act, slope, _stream()), x, w, y,
+               "conv_wino fwd")
+
+
+def _fwd_nc8(pl, x, w, b, y, act, slope, frozen_w, keep):
+    """Routes k333_nc8 (3x3x3: (sample, frame) images, (time tap, channel) chunks) and s2_nc8 (4x4 stride 2: input parity planes)."""
+    L = _lib.lib()
+    N, Cin, Cout, Ti, Hi, Wi = pl.dims[0:6]
+    if pl.fwd_route == "k333_nc8":
+        A = _packed(w, frozen_w, ("fwd-bf16-k333",), lambda: _pack_bf16_k333(w, Cout, Cin))
+        run = lambda: L.c2m_conv3d_nc8(_p(A), _p(_to_nc8(x, keep)), _p(y), _p(b), Cout, Cin, N, Ti, Hi, Wi, int(pl.reflect), 1, act, slope,
+                                       _stream())
+    else:
+        A = _packed(w, frozen_w, ("fwd-bf16-s2",), lambda: _pack_bf16_patch(w, Cout, Cin, pl.K, 16, 2))
+        run = lambda: L.c2m_conv_s2_nc8(_p(A), _p(_to_nc8(x, keep)), _p(y), _p(b), Cout, Cin, N, Hi, Wi, int(pl.reflect), 1, act, slope,
+                                        _stream())
+    _fwd_timed(pl, run, x, w, y, "conv_nc8 fwd")
+
+
+def _fwd_igemm(pl, x, w, b, y, act, slope, frozen_w, keep):
+    """Routes igemm, patch_nc8 (c2m_conv_patch_nc8 on channel-blocked input) and g8 (the NC8 gather form: channel-blocked input, bf16
+    weights in (tap, chunk) order -- conv_gather_nc8_kernel), each with its split-K reduction."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    route = pl.fwd_route
+    S = pl.g8_fwd_splits if route == "g8" else pl.fwd_splits
+    dst = y if S == 1 else torch.empty(S * y.numel(), device=x.device, dtype=torch.float32)
+    if route == "g8":
+        A = _packed(w, frozen_w, ("fwd-bf16-g8",), lambda: _pack_bf16_gather(w, Cout, Cin, pl.dims[9:12], (1, 1, 1), pl.K, pl.K // Cin))
+
+        def run():
+            xn = _to_nc8(x)
+            _set_io(pl.g8_fwd_geom, xn, BF16)
+            return L.c2m_conv_igemm(_p(A), _p(xn), _p(dst), None, _p(b), _p(pl.g8_fwd_tab), _gp(pl.g8_fwd_geom), act, slope, _stream())
+    else:
+        if pl.bf16 and pl.fwd_geom[G.PATCH]:       # (the patch kernels of the bf16 path read their own weight image)
+            A = _packed(w, frozen_w, ("fwd-bf16-patch",), lambda: _pack_bf16_patch(w, Cout, Cin, pl.K, 9))
+        else:
+            A = _packed(w, frozen_w, ("fwd", pl.ck), lambda: _pack_native(w, Cout, Cin, pl.ck, pl.dims[9:12], (1, 1, 1), pl.K, pl.K // Cin))
+        _set_io(pl.fwd_geom, x, y.dtype)
+        if route == "patch_nc8":
+            run = lambda: _nc8_launch(L, A, x, dst, None, b, pl.fwd_geom, act, slope, keep)
+        else:
+            run = lambda: L.c2m_conv_igemm(_p(A), _p(x), _p(dst), None, _p(b), _p(pl.fwd_tab), _gp(pl.fwd_geom), act, slope, _stream())
+    _fwd_timed(pl, run, x, w, y, "conv_igemm fwd (NC8 gather)" if route == "g8" else "conv_igemm fwd")
+    if S > 1:
+        _lib.check(L.c2m_splitk_reduce(_p(dst), _p(y), _p(b), y.numel(), S, int(pl.fwd_geom[G.OUT_SC]), Cout, act, slope, _dt(y),
+                                       _stream()), "splitk_reduce")
+
+
+_FWD = {"wino3d": _fwd_wino, "wino4": _fwd_wino, "wino": _fwd_wino, "k333_nc8": _fwd_nc8, "s2_nc8": _fwd_nc8,
+        "g8": _fwd_igemm, "patch_nc8": _fwd_igemm, "igemm": _fwd_igemm}
+
+
+def _wgrad_timed(pl, run, nbytes, what):
+    _lib.check(_timed(pl.wgrad_prof[0], pl.fwd_flops, run, pl.wgrad_prof[1], nbytes), what)
+
+
+def _wgrad_nc8(pl, x, w, gy, keep, x_keep):
+    """Routes nc8 (3x3 stride 1), s2_nc8 (4x4 stride 2) and k333_nc8 (3x3x3, one launch per time tap): both operands in NC8 form -- X
+    from the forward launch (x_keep = ctx.nc8_keep) or converted now, dY shared with the data gradient (keep)."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    gyn = _to_nc8(_as(gy, BF16), keep)
+    xn = next(iter(x_keep.values()))[1] if x_keep else _to_nc8(_as(x, BF16))
+    gw = torch.empty_like(w)
+    gb = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    if pl.wgrad_route == "k333_nc8":
+        Ti, Hi, Wi = pl.dims[3:6]
+        slab = torch.empty(L.c2m_conv_wgrad_nc8_slab_floats(Cout, Cin, N * Ti, Hi, Wi, 0), device=x.device, dtype=torch.float32)
+        what = "conv_wgrad3d_nc8"
+        run = lambda: L.c2m_conv_wgrad3d_nc8(_p(gyn), _p(xn), _p(slab), _p(gw), _p(gb), Cout, Cin, N, Ti, Hi, Wi, int(pl.reflect), _stream())
+    else:
+        s2 = int(pl.wgrad_route == "s2_nc8")
+        Ho, Wo = pl.dims[7:9]                  # the dY map
+        slab = torch.empty(L.c2m_conv_wgrad_nc8_slab_floats(Cout, Cin, N, Ho, Wo, s2), device=x.device, dtype=torch.float32)
+        what = "conv_wgrad_nc8"
+        run = lambda: L.c2m_conv_wgrad_nc8(_p(gyn), _p(xn), _p(slab), _p(gw), _p(gb), Cout, Cin, N, Ho, Wo, int(pl.reflect), s2, _stream())
+    _wgrad_timed(pl, run, 2 * (gyn.numel() + xn.numel()) + 4 * w.numel(), what)
+    return gw, gb
+
+
+def _wgrad_wino(pl, x, w, gy, keep, x_keep):
+    """Routes wino and wino3d (the 2-D kernel over (sample, frame) images and virtual channels (time tap, channel))."""
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    Ti, Hi, Wi = pl.dims[3:6]
+    S = pl.wino_wg_splits
+    nbytes = 4 * (gy.numel() + x.numel() + w.numel())
+    slab = torch.empty((S + 1) * 16 * Cout * pl.dims[9] * Cin, device=x.device, dtype=torch.float32)
+    dbslab = torch.empty(S * Cout, device=x.device, dtype=torch.float32)
+    gb = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    if pl.wgrad_route == "wino3d":
+        gw3 = torch.empty(Cout, 3, Cin, 3, 3, device=x.device, dtype=torch.float32)      # (time tap, channel) order
+        _wgrad_timed(pl, lambda: L.c2m_conv_wino_wgrad3d(_p(gy), _p(x), _p(slab), _p(dbslab), _p(gw3), _p(gb), Cout, Cin, N, Ti, Hi, Wi,
+                                                         int(pl.reflect), _stream()), nbytes, "conv_wino_wgrad3d")
+        return gw3.permute(0, 2, 1, 3, 4).contiguous(), gb
+    gw = torch.empty_like(w)
+    _wgrad_timed(pl, lambda: L.c2m_conv_wino_wgrad(_p(gy), _p(x), _p(slab), _p(dbslab), _p(gw), _p(gb), Cout, Cin, N, Hi, Wi,
+                                                   int(pl.reflect), _stream()), nbytes, "conv_wino_wgrad")
+    return gw, gb
+
+
+def _wgrad_igemm(pl, x, w, gy, keep, x_keep):
+    L = _lib.lib()
+    N, Cin, Cout = pl.dims[0:3]
+    slab = torch.empty(pl.wg_splits * Cout * pl.J, device=x.device, dtype=torch.float32)
+    gw = torch.empty_like(w)
+    gb = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    # bf16 data path: the MFMA kernel gathers bf16 dY and X; the <= 4-output-channel heads run on the fp32 vector-ALU
+    # kernels (c2m_conv_wgrad's own rule: M <= 4 and >= 16384 pixels)
+    wdt = BF16 if (pl.bf16 and not (Cout <= 4 and int(pl.wg_geom[G.NPIX]) >= 16384)) else torch.float32
+    xg, gyw = _as(x, wdt), _as(gy, wdt)
+    pl.wg_geom[G.X_BYTES], pl.wg_geom[G.DY_BYTES] = xg.numel() * xg.element_size(), gyw.numel() * gyw.element_size()
+    pl.wg_geom[G.X_TYPE] = _dt(xg)
+    _wgrad_timed(pl, lambda: L.c2m_conv_wgrad(_p(gyw), _p(xg), _p(slab), _p(gw), _p(gb), _p(pl.wg_tab), _gp(pl.wg_geom), _stream()),
+                 xg.element_size() * (gyw.numel() + xg.numel()) + 4 * w.numel(), "conv_wgrad")
+    return gw, gb
+
+
+_WGRAD = {"k333_nc8": _wgrad_nc8, "nc8": _wgrad_nc8, "s2_nc8": _wgrad_nc8, "wino3d": _wgrad_wino, "wino": _wgrad_wino,
+          "igemm": _wgrad_igemm}
 
 
 class _ConvFn(torch.autograd.Function):
@@ -1618,122 +1786,23 @@ class _ConvFn(torch.autograd.Function):
         ctx.wb_refs = (weakref.ref(w), weakref.ref(b) if b is not None else None)
         x, w = _f(x), _f(w)
         pl = _plan(x, w, stride, pad, reflect, dgrad_rows)
-        L = _lib.lib()
-        N, Cin, Cout = pl.dims[0:3]
-        if b is not None and b.numel() != Cout:
-            raise RuntimeError(f"convolution: bias of {b.numel()} elements for {Cout} output channels")
+        if b is not None and b.numel() != pl.dims[2]:
+            raise RuntimeError(f"convolution: bias of {b.numel()} elements for {pl.dims[2]} output channels")
         ctx.frozen_w = not ctx.needs_input_grad[1]
         ctx.x_dtype = x.dtype
-        ctx.nc8_keep = None
-        if not pl.bf16:
-            x = _as(x, torch.float32)            # the fp32 kernels are fp32 in, fp32 out
-        if pl.wino_fwd:
-            if pl.wino3d:      # virtual channels (kt, ci): [Cout][3*Cin][3][3]
-                U = _packed(w, ctx.frozen_w, ("wino-fwd3d",), lambda: _wino_filter(
-                    w.permute(0, 2, 1, 3, 4).reshape(Cout, 3 * Cin, 3, 3).contiguous(), Cout, 3 * Cin, 0))
-            elif pl.wino4_fwd:
-                U = _packed(w, ctx.frozen_w, ("wino4-fwd",), lambda: _wino4_filter(w, Cout, Cin, 0))
-            else:
-                U = _packed(w, ctx.frozen_w, ("wino-fwd",), lambda: _wino_filter(w, Cout, Cin, 0))
-            conv_wino = L.c2m_conv_wino4 if (pl.wino4_fwd and not pl.wino3d) else L.c2m_conv_wino
-            y = torch.empty(pl.out_shape, device=x.device, dtype=torch.float32)
-            w4 = pl.wino4_fwd and not pl.wino3d           # F(4x4,3x3): its own roofline family (executed = algorithmic / 4)
-            tag = ("fwd", Cout, pl.K, int(pl.fwd_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "wino4" if w4 else "wino")
-            _lib.check(_timed("wino4" if w4 else "wino", 2.0 * Cout * pl.K * int(pl.fwd_geom[G.NPIX]),
-                              lambda: conv_wino(_p(U), _p(x), _p(y), None, _p(b), _gp(pl.wino_fwd_geom), ACT[act],
-                                                slope, _stream()), tag,
-                              4 * (x.numel() + w.numel() + y.numel())), "conv_wino fwd")
-            ctx.pl, ctx.act, ctx.has_bias = pl, act, b is not None
-            ctx.save_for_backward(x, w, y if ACT[act] else None)
-            return _tag_conv_output(ctx, pl, y, act)
-        if pl.bf16 and pl.k333_nc8:
-            x = _as(x, BF16)
-            A = _packed(w, ctx.frozen_w, ("fwd-bf16-k333",), lambda: _pack_bf16_k333(w, Cout, Cin))
-            y = torch.empty(pl.out_shape, device=x.device, dtype=BF16)
-            Ti_, Hi_, Wi_ = pl.dims[3:6]
-            tag = ("fwd", Cout, pl.K, int(pl.fwd_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
-            ctx.nc8_keep = {} if (pl.k333_wgrad_nc8 and ctx.needs_input_grad[1]) else None
-
-            def run_k333():
-                xn = _to_nc8(x, ctx.nc8_keep)
-                return L.c2m_conv3d_nc8(_p(A), _p(xn), _p(y), _p(b), Cout, Cin, N, Ti_, Hi_, Wi_, int(pl.reflect), 1, ACT[act], slope,
-                                        _stream())
-            _lib.check(_timed("igemm_bf16", 2.0 * Cout * pl.K * int(pl.fwd_geom[G.NPIX]), run_k333, tag,
-                              2 * (x.numel() + y.numel()) + 4 * w.numel()), "conv3d_nc8 fwd")
-            ctx.pl, ctx.act, ctx.has_bias = pl, act, b is not None
-            ctx.save_for_backward(x, w, y if ACT[act] else None)
-            return _tag_conv_output(ctx, pl, y, act)
-        if pl.bf16 and pl.s2_nc8:
-            x = _as(x, BF16)
-            A = _packed(w, ctx.frozen_w, ("fwd-bf16-s2",), lambda: _pack_bf16_patch(w, Cout, Cin, pl.K, 16, 2))
-            y = torch.empty(pl.out_shape, device=x.device, dtype=BF16)
-            Hi_, Wi_ = pl.dims[4:6]
-            tag = ("fwd", Cout, pl.K, int(pl.fwd_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
-
-            ctx.nc8_keep = {} if (pl.s2_wgrad_nc8 and ctx.needs_input_grad[1]) else None
-
-            def run_s2():
-                xn = _to_nc8(x, ctx.nc8_keep)
-                return L.c2m_conv_s2_nc8(_p(A), _p(xn), _p(y), _p(b), Cout, Cin, N, Hi_, Wi_, int(pl.reflect), 1, ACT[act], slope,
-                                         _stream())
-            _lib.check(_timed("igemm_bf16", 2.0 * Cout * pl.K * int(pl.fwd_geom[G.NPIX]), run_s2, tag,
-                              2 * (x.numel() + y.numel()) + 4 * w.numel()), "conv_s2_nc8 fwd")
-            ctx.pl, ctx.act, ctx.has_bias = pl, act, b is not None
-            ctx.save_for_backward(x, w, y if ACT[act] else None)
-            return _tag_conv_output(ctx, pl, y, act)
-        if pl.bf16 and pl.g8_fwd:
-            # the NC8 gather form: channel-blocked input, bf16 weights in (tap, chunk) order (conv_gather_nc8_kernel)
-            x = _as(x, BF16)
-            A = _packed(w, ctx.frozen_w, ("fwd-bf16-g8",), lambda: _pack_bf16_gather(w, Cout, Cin, pl.dims[9:12], (1, 1, 1), pl.K, pl.K // Cin))
-            S = pl.g8_fwd_splits
-            y = torch.empty(pl.out_shape, device=x.device, dtype=BF16)
-            dst = y if S == 1 else torch.empty(S * y.numel(), device=x.device, dtype=torch.float32)
-            tag = ("fwd", Cout, pl.K, int(pl.fwd_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, S, "nc8g")
-
-            def run_g8():
-                xn = _to_nc8(x)
-                _set_io(pl.g8_fwd_geom, xn, BF16)
-                return L.c2m_conv_igemm(_p(A), _p(xn), _p(dst), None, _p(b), _p(pl.g8_fwd_tab), _gp(pl.g8_fwd_geom), ACT[act], slope,
-                                        _stream())
-            _lib.check(_timed("igemm_bf16", 2.0 * Cout * pl.K * int(pl.fwd_geom[G.NPIX]), run_g8, tag,
-                              2 * (x.numel() + y.numel()) + 4 * w.numel()), "conv_igemm fwd (NC8 gather)")
-            if S > 1:
-                _lib.check(L.c2m_splitk_reduce(_p(dst), _p(y), _p(b), y.numel(), S, int(pl.fwd_geom[G.OUT_SC]), Cout, ACT[act],
-                                               slope, _dt(y), _stream()), "splitk_reduce")
-            ctx.pl, ctx.act, ctx.has_bias = pl, act, b is not None
-            ctx.save_for_backward(x, w, y if ACT[act] else None)
-            return _tag_conv_output(ctx, pl, y, act)
-        if pl.fwd_patch and pl.bf16:
-            A = _packed(w, ctx.frozen_w, ("fwd-bf16-patch",), lambda: _pack_bf16_patch(w, Cout, Cin, pl.K, 9))
-        else:
-            A = _packed(w, ctx.frozen_w, ("fwd", pl.ck), lambda: _pack_native(w, Cout, Cin, pl.ck, pl.dims[9:12], (1, 1, 1), pl.K, pl.K // Cin))
-        S = pl.fwd_splits
-        ydt = torch.float32
-        if pl.bf16:
-            # bf16 data path: bf16 in (an fp32 input is cast once), bf16 out -- except the <= 4-channel heads (flow, occlusion,
-            # RGB), which stay fp32 and run on the fp32 vector-ALU kernels when the launch is big enough for them
-            if _thin(Cout, S, int(pl.fwd_geom[G.NPIX])):
-                x = _as(x, torch.float32)
-            else:
-                x = _as(x, BF16)
-                ydt = BF16 if Cout > 4 else torch.float32
-        y = torch.empty(pl.out_shape, device=x.device, dtype=ydt)
-        dst = y if S == 1 else torch.empty(S * y.numel(), device=x.device, dtype=torch.float32)
-        tag = ("fwd", Cout, pl.K, int(pl.fwd_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, S)
-        _set_io(pl.fwd_geom, x, ydt)
-        nc8 = pl.fwd_patch and pl.bf16 and pl.nc8
-        ctx.nc8_keep = {} if (nc8 and pl.wgrad_nc8 and ctx.needs_input_grad[1]) else None      # X in NC8 form, for the weight gradient
-        _lib.check(_timed("igemm_bf16" if pl.bf16 else "igemm", 2.0 * Cout * pl.K * int(pl.fwd_geom[G.NPIX]),
-                          (lambda: _nc8_launch(L, A, x, dst, None, b, pl.fwd_geom, ACT[act], slope, ctx.nc8_keep)) if nc8 else
-                          (lambda: L.c2m_conv_igemm(_p(A), _p(x), _p(dst), None, _p(b), _p(pl.fwd_tab), _gp(pl.fwd_geom),
-                                                    ACT[act], slope, _stream())), tag + (("nc8",) if nc8 else ()),
-                          x.element_size() * x.numel() + 4 * w.numel() + y.element_size() * y.numel()), "conv_igemm fwd")
-        if S > 1:
-            _lib.check(L.c2m_splitk_reduce(_p(dst), _p(y), _p(b), y.numel(), S, int(pl.fwd_geom[G.OUT_SC]), Cout, ACT[act],
-                                           slope, _dt(y), _stream()), "splitk_reduce")
+        ctx.nc8_keep = {} if (pl.keep_x_nc8 and ctx.needs_input_grad[1]) else None      # X in NC8 form, for the weight gradient
+        x = _as(x, pl.fwd_xdt)             # (the fp32 kernels are fp32 in, fp32 out; bf16 path: an fp32 input is cast once)
+        y = torch.empty(pl.out_shape, device=x.device, dtype=pl.fwd_ydt)
+        _FWD[pl.fwd_route](pl, x, w, b, y, ACT[act], slope, ctx.frozen_w, ctx.nc8_keep)
         ctx.pl, ctx.act, ctx.has_bias = pl, act, b is not None
         ctx.save_for_backward(x, w, y if ACT[act] else None)
-        return _tag_conv_output(ctx, pl, y, act)
+        # an output whose gradient this layer's backward will read through NC8 kernels only (no fused activation: act_bwd reads the
+        # incoming gradient in NCHW): a norm op told that it is the output's ONLY consumer (`private_input=True`) then hands its dx back
+        # in NC8 form alone
+        if pl.bf16 and not ACT[act] and y.dtype == BF16 and _bwd_reads_only_nc8(
+                pl, ctx.needs_input_grad[0], ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])):
+            y._c2m_bwd_nc8 = True
+        return y
 
     @staticmethod
     def backward(ctx, gy):
@@ -1742,10 +1811,10 @@ class _ConvFn(torch.autograd.Function):
         gy = _f(gy)
         if _NC8_LOG is not None:
             _NC8_LOG_TAG[0] = " (own act_bwd)" if ACT[ctx.act] else " (incoming gradient)"
+        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         if ACT[ctx.act]:
             gy = _as(gy, y.dtype)
-            need_w0 = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-            if y.dtype == BF16 and _bwd_reads_only_nc8(pl, ctx.needs_input_grad[0], need_w0):
+            if y.dtype == BF16 and _bwd_reads_only_nc8(pl, ctx.needs_input_grad[0], need_w):
                 # the masked gradient in NC8 form only: its readers below are all NC8 kernels (no NCHW write, no layout pass)
                 Nn, Cc = y.shape[0], y.shape[1]
                 gn = torch.empty((Nn, _cdiv(Cc, 8)) + tuple(y.shape[2:]) + (8,), device=y.device, dtype=BF16)
@@ -1758,7 +1827,6 @@ class _ConvFn(torch.autograd.Function):
                 gy = g
         N, Cin, Cout = pl.dims[0:3]
         gx = gw = gb = None
-        need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
         # The weight gradient and the data gradient of a layer are independent: with both wanted, the weight gradient (and its
         # split reductions) is issued on a side stream and joined at the end of this node, so the two launches share the chip
         # -- the tail of one (e.g. 1440 workgroups on 512 slots) is filled by the other and the ~10 us reductions disappear
@@ -1770,8 +1838,8 @@ class _ConvFn(torch.autograd.Function):
         side = _side_stream(x.device) if (side_on and need_w and ctx.needs_input_grad[0] and not _on_aux_stream(x.device)) else None
         # NC8 form of dY: one layout pass shared by the data gradient and the weight gradient of this node (made on the main
         # stream BEFORE a fork, so the side stream's launch is ordered behind it)
-        keep = {} if (pl.bf16 and (pl.nc8 or pl.k333_wgrad_nc8 or pl.k333_dgrad_nc8)) else None
-        if keep is not None and need_w and (pl.wgrad_nc8 or pl.s2_wgrad_nc8 or pl.k333_wgrad_nc8):
+        keep = {} if pl.keep_dy_nc8 else None
+        if need_w and pl.wgrad_route in _NC8_WGRADS:
             gy = _as(gy, BF16)
             _to_nc8(gy, keep)
         # (not while capturing a HIP graph: the graph executor runs the long side branch worse than the per-node fork + join below --
@@ -1846,84 +1914,12 @@ class _ConvFn(torch.autograd.Function):
 
     @staticmethod
     def _wgrad(ctx, pl, x, w, gy, keep=None):
-        L = _lib.lib()
-        N, Cin, Cout = pl.dims[0:3]
-        gw = gb = None
+        if not (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])):
+            return None, None
         if not pl.bf16:
             gy = _as(gy, torch.float32)
-        want = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        if want and pl.bf16 and pl.k333_wgrad_nc8:
-            Ti, Hi, Wi = pl.dims[3:6]
-            gyn = _to_nc8(_as(gy, BF16), keep)
-            xn = next(iter(ctx.nc8_keep.values()))[1] if ctx.nc8_keep else _to_nc8(_as(x, BF16))
-            slab = torch.empty(L.c2m_conv_wgrad_nc8_slab_floats(Cout, Cin, N * Ti, Hi, Wi, 0), device=x.device, dtype=torch.float32)
-            gw = torch.empty_like(w)
-            gb_t = torch.empty(Cout, device=x.device, dtype=torch.float32)
-            tag = ("wgrad", Cout, pl.K, int(pl.wg_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
-            _lib.check(_timed("wgrad_bf16", 2.0 * Cout * pl.K * int(pl.wg_geom[G.NPIX]),
-                              lambda: L.c2m_conv_wgrad3d_nc8(_p(gyn), _p(xn), _p(slab), _p(gw), _p(gb_t), Cout, Cin, N, Ti, Hi, Wi,
-                                                             int(pl.reflect), _stream()), tag,
-                              2 * (gyn.numel() + xn.numel()) + 4 * w.numel()), "conv_wgrad3d_nc8")
-            return gw, (gb_t if ctx.has_bias else None)
-        if want and pl.bf16 and (pl.wgrad_nc8 or pl.s2_wgrad_nc8):
-            # both operands in NC8 form: X from the forward launch (ctx.nc8_keep) or converted now, dY shared with the data gradient
-            s2 = int(pl.s2_wgrad_nc8)
-            Hi, Wi = pl.dims[7:9]                  # the dY map
-            gyn = _to_nc8(_as(gy, BF16), keep)
-            xn = next(iter(ctx.nc8_keep.values()))[1] if ctx.nc8_keep else _to_nc8(_as(x, BF16))
-            slab = torch.empty(L.c2m_conv_wgrad_nc8_slab_floats(Cout, Cin, N, Hi, Wi, s2), device=x.device, dtype=torch.float32)
-            gw = torch.empty_like(w)
-            gb_t = torch.empty(Cout, device=x.device, dtype=torch.float32)
-            tag = ("wgrad", Cout, pl.K, int(pl.wg_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "nc8")
-            _lib.check(_timed("wgrad_bf16", 2.0 * Cout * pl.K * int(pl.wg_geom[G.NPIX]),
-                              lambda: L.c2m_conv_wgrad_nc8(_p(gyn), _p(xn), _p(slab), _p(gw), _p(gb_t), Cout, Cin, N, Hi, Wi,
-                                                           int(pl.reflect), s2, _stream()), tag,
-                              2 * (gyn.numel() + xn.numel()) + 4 * w.numel()), "conv_wgrad_nc8")
-            return gw, (gb_t if ctx.has_bias else None)
-        if (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) and pl.wino_wgrad and pl.wino_wgrad3d:
-            S = pl.wino_wg_splits
-            Ti, Hi, Wi = pl.dims[3:6]
-            slab = torch.empty((S + 1) * 16 * Cout * 3 * Cin, device=x.device, dtype=torch.float32)
-            dbslab = torch.empty(S * Cout, device=x.device, dtype=torch.float32)
-            gw3 = torch.empty(Cout, 3, Cin, 3, 3, device=x.device, dtype=torch.float32)      # (time tap, channel) order
-            gb_t = torch.empty(Cout, device=x.device, dtype=torch.float32)
-            tag = ("wgrad", Cout, pl.K, int(pl.wg_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "wino")
-            _lib.check(_timed("wino_wgrad", 2.0 * Cout * pl.K * int(pl.wg_geom[G.NPIX]),
-                              lambda: L.c2m_conv_wino_wgrad3d(_p(gy), _p(x), _p(slab), _p(dbslab), _p(gw3), _p(gb_t), Cout,
-                                                              Cin, N, Ti, Hi, Wi, int(pl.reflect), _stream()), tag,
-                              4 * (gy.numel() + x.numel() + w.numel())), "conv_wino_wgrad3d")
-            gw = gw3.permute(0, 2, 1, 3, 4).contiguous()
-            gb = gb_t if ctx.has_bias else None
-        elif (ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])) and pl.wino_wgrad:
-            S = pl.wino_wg_splits
-            slab = torch.empty((S + 1) * 16 * Cout * Cin, device=x.device, dtype=torch.float32)
-            dbslab = torch.empty(S * Cout, device=x.device, dtype=torch.float32)
-            gw = torch.empty_like(w)
-            gb_t = torch.empty(Cout, device=x.device, dtype=torch.float32)
-            Hi, Wi = pl.dims[4:6]
-            tag = ("wgrad", Cout, pl.K, int(pl.wg_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, "wino")
-            _lib.check(_timed("wino_wgrad", 2.0 * Cout * pl.K * int(pl.wg_geom[G.NPIX]),
-                              lambda: L.c2m_conv_wino_wgrad(_p(gy), _p(x), _p(slab), _p(dbslab), _p(gw), _p(gb_t), Cout,
-                                                            Cin, N, Hi, Wi, int(pl.reflect), _stream()), tag,
-                              4 * (gy.numel() + x.numel() + w.numel())), "conv_wino_wgrad")
-            gb = gb_t if ctx.has_bias else None
-        elif ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            slab = torch.empty(pl.wg_splits * Cout * pl.J, device=x.device, dtype=torch.float32)
-            gw = torch.empty_like(w)
-            gb_t = torch.empty(Cout, device=x.device, dtype=torch.float32)
-            tag = ("wgrad", Cout, pl.K, int(pl.wg_geom[G.NPIX]), pl.dims[9:12], pl.stride, pl.reflect, pl.wg_splits)
-            # bf16 data path: the MFMA kernel gathers bf16 dY and X; the <= 4-output-channel heads run on the fp32 vector-ALU
-            # kernels (c2m_conv_wgrad's own rule: M <= 4 and >= 16384 pixels)
-            wdt = BF16 if (pl.bf16 and not (Cout <= 4 and int(pl.wg_geom[G.NPIX]) >= 16384)) else torch.float32
-            xg, gyw = _as(x, wdt), _as(gy, wdt)
-            pl.wg_geom[G.X_BYTES], pl.wg_geom[G.DY_BYTES] = xg.numel() * xg.element_size(), gyw.numel() * gyw.element_size()
-            pl.wg_geom[G.X_TYPE] = _dt(xg)
-            _lib.check(_timed("wgrad_bf16" if pl.bf16 else "wgrad", 2.0 * Cout * pl.K * int(pl.wg_geom[G.NPIX]),
-                              lambda: L.c2m_conv_wgrad(_p(gyw), _p(xg), _p(slab), _p(gw), _p(gb_t), _p(pl.wg_tab),
-                                                       _gp(pl.wg_geom), _stream()), tag,
-                              xg.element_size() * (gyw.numel() + xg.numel()) + 4 * w.numel()), "conv_wgrad")
-            gb = gb_t if ctx.has_bias else None
-        return gw, gb
+        gw, gb = _WGRAD[pl.wgrad_route](pl, x, w, gy, keep, ctx.nc8_keep)
+        return gw, (gb if ctx.has_bias else None)
 
 
 def conv(x, w, b=None, stride=1, padding=0, padding_mode="zeros", act=None, dgrad_channels=None, slope=LRELU_SLOPE):
@@ -2049,16 +2045,7 @@ def conv_transpose2d(x, w, b=None, stride=2, padding=1, act=None, slope=LRELU_SL
     s3, p3 = _triple(stride, 2), _pad3(padding, 2)
     Ho, Wo = (H - 1) * s3[1] - 2 * p3[1] + kh, (W - 1) * s3[2] - 2 * p3[2] + kw
     # the forward convolution whose data gradient this is: input [N, Co, Ho, Wo] (x of the plan), weight [Ci, Co, kh, kw]
-    key = ((N, Co, Ho, Wo), tuple(w.shape), s3, p3, False, x.device.index, _conv_bf16, None)
-    pl = _geom_cache.get(key)
-    if pl is None:
-        pl = _geom_cache[key] = _ConvPlan((N, Co, Ho, Wo), tuple(w.shape), s3, p3, False, x.device, _conv_bf16, None)
-        if _conv_bf16:
-            pl.fwd_geom[G.PRECISION] = pl.wg_geom[G.PRECISION] = 1
-            for c in pl.classes:
-                c["geom"][G.PRECISION] = 1
-            for grp in (pl.cls_batch["groups"] if pl.cls_batch else ()):
-                grp["geom"][G.PRECISION] = 1
+    pl = _plan_for((N, Co, Ho, Wo), tuple(w.shape), s3, p3, False, x.device)
     if pl.out_shape != (N, Ci, H, W):
         raise ValueError(f"conv_transpose2d: inconsistent geometry {tuple(x.shape)} vs {pl.out_shape}")
     with torch.no_grad():

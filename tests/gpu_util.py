@@ -105,7 +105,7 @@ def stretch_wgrads(monkeypatch, ops, ms):
         cur = torch.cuda.current_stream(x.device)
         if any(cur == s for s in ops._side_streams.values()):
             st.stretched += 1
-            st.nc8 += bool(pl.bf16 and (pl.wgrad_nc8 or pl.s2_wgrad_nc8 or pl.k333_wgrad_nc8))      # (NC8 operands riding on x / dY)
+            st.nc8 += pl.wgrad_route in ops._NC8_WGRADS      # (NC8 operands riding on x / dY)
             stretch(cur, st.ms)
         return orig(ctx, pl, x, w, gy, keep)
 
