@@ -22,6 +22,24 @@ __device__ __forceinline__ void warp_source(float fx, float fy, int x, int y, in
     iy = fmaf(gy + 1.0f, (float)H / 2.0f, -0.5f);
 }
 
+// The same rule at a fractional position, read on a larger grid (detail_warp.hip): (xl, yl) is a position on the h x w grid the
+// flow lives on, (fx, fy) the flow there in h x w pixels, and (ix, iy) the position read on an H x W grid covering the same
+// image, BEFORE the border clamp.  In real numbers ix = (xl + fx) * W / (w - 1) - 0.5.  At an integer position with H == h and
+// W == w every operation below is warp_source's, so the two agree bit for bit (h, w >= 2).
+__device__ __forceinline__ float lin_m1_1_at(float p, int steps) {
+    const float step = 2.0f / (float)(steps - 1);
+    return p < (float)(steps / 2) ? fmaf(step, p, -1.0f) : fmaf(-step, (float)(steps - 1) - p, 1.0f);
+}
+
+__device__ __forceinline__ void warp_source_at(float fx, float fy, float xl, float yl, int h, int w, int H, int W, float& ix,
+                                               float& iy) {
+    const float cx = (float)(((double)w - 1.0) / 2.0), cy = (float)(((double)h - 1.0) / 2.0);
+    const float gx = lin_m1_1_at(xl, w) + fx / cx;
+    const float gy = lin_m1_1_at(yl, h) + fy / cy;
+    ix = fmaf(gx + 1.0f, (float)W / 2.0f, -0.5f);
+    iy = fmaf(gy + 1.0f, (float)H / 2.0f, -0.5f);
+}
+
 // padding_mode="border" (ATen clip_coordinates): into [0, n - 1]; a NaN coordinate becomes 0
 __device__ __forceinline__ float warp_border(float i, int n) { return fminf((float)(n - 1), fmaxf(i, 0.0f)); }
 

@@ -2754,6 +2754,79 @@ def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fil
     return out_f, out_i
 
 
+# ============================================================================ dataset-resolution output (csrc/detail_warp.hip)
+def _detail_warp_plan(frame_u8, generated, warped, flow, occ, ids, occ_threshold):
+    """Shapes and dtypes of detail_warp, checked before anything is launched: (B, T, h, w, H, W)."""
+    if generated.dim() != 5 or generated.shape[1] != 3:
+        raise ValueError(f"generated must be [B,3,T,h,w], got {tuple(generated.shape)}")
+    B, _, T, h, w = generated.shape
+    if h < 2 or w < 2:
+        raise ValueError(f"the working size must be at least 2x2 (the flow's coordinate rule divides by h - 1, w - 1), got {h}x{w}")
+    for name, t, c, dtypes in (("generated", generated, 3, (torch.float32, torch.bfloat16)),
+                               ("warped", warped, 3, (torch.float32, torch.bfloat16)),
+                               ("flow", flow, 2, (torch.float32,)), ("occ", occ, 1, (torch.float32, torch.bfloat16))):
+        if t is None and name == "occ":
+            continue
+        if tuple(t.shape) != (B, c, T, h, w):
+            raise ValueError(f"{name} must be {(B, c, T, h, w)} for generated {tuple(generated.shape)}, got {tuple(t.shape)}")
+        if t.dtype not in dtypes:
+            raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}"
+                             f"{' (coordinates are never rounded)' if name == 'flow' else ''}, got {t.dtype}")
+    if frame_u8.dtype != torch.uint8:
+        raise ValueError(f"frame_u8 must be uint8, got {frame_u8.dtype}")
+    if frame_u8.dim() != 4 or frame_u8.shape[0] != B or frame_u8.shape[3] != 3:
+        raise ValueError(f"frame_u8 must be [{B},H,W,3], got {tuple(frame_u8.shape)}")
+    H, W = frame_u8.shape[1:3]
+    if H < h or W < w:
+        raise ValueError(f"the output size {H}x{W} is below the working size {h}x{w}: down-scaling is not supported")
+    if H * W * 3 >= 2 ** 31:
+        raise ValueError(f"one {H}x{W} frame has 2^31 bytes or more")
+    if ids is not None:
+        if ids.dtype != torch.int32:
+            raise ValueError(f"ids must be int32, got {ids.dtype}")
+        if tuple(ids.shape) != (B, H, W):
+            raise ValueError(f"ids must be {(B, H, W)} for frame_u8 {tuple(frame_u8.shape)}, got {tuple(ids.shape)}")
+    if occ_threshold is not None:
+        if ids is None:
+            raise ValueError("occ_threshold marks disoccluded ids: it needs ids")
+        if occ is None:
+            raise ValueError("a threshold needs occ")
+    return B, T, h, w, H, W
+
+
+def detail_warp(frame_u8, generated, warped, flow, occ=None, ids=None, occ_threshold=None, fill_id=0):
+    """Predicted frames at the size of `frame_u8`: its sharp pixels moved along the working-size backward flow, the generator's
+    output supplying the rest.  With up() the bilinear enlargement (align_corners=False) and warpF the bilinear value of
+    frame_u8 where the working-size warp reads, mapped to the large grid (csrc/warp_coord.h, border clamp included):
+        level = floor(clip(255 up(generated) + up(occ) * (warpF - 255 up(warped)), 0, 255) + 0.5)
+
+    frame_u8 [B,H,W,3] uint8: the last input frame at the output size; generated, warped [B,3,T,h,w] (fp32 or bf16), warped =
+    flow_warp of the working-size frame by `flow`, no occlusion; flow [B,2,T,h,w] fp32 in working-size pixels; occ [B,1,T,h,w]
+    or None (1 everywhere); 2 <= h <= H, 2 <= w <= W.  ids [B,H,W] int32: carried to the nearest pixel of the same position, never
+    blended; with occ_threshold, fill_id where up(occ) < occ_threshold.
+    Returns (uint8 [B,T,H,W,3], int32 [B,T,H,W] or None).  One launch, no atomics, no autograd."""
+    ts = (frame_u8, generated, warped, flow, occ, ids)
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    B, T, h, w, H, W = _detail_warp_plan(frame_u8, generated, warped, flow, occ, ids, occ_threshold)
+    if not -2 ** 31 <= int(fill_id) < 2 ** 31:
+        raise ValueError(f"fill_id must be an int32 value, got {fill_id}")
+    for t in ts:
+        if t is not None and t.device.index != _cur_device():
+            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    frame_u8, ids = _f(frame_u8), None if ids is None else _f(ids)
+    generated, warped = _as(generated.detach(), torch.float32), _as(warped.detach(), torch.float32)
+    flow, occ = _f(flow.detach()), None if occ is None else _as(occ.detach(), torch.float32)
+    out = torch.empty(B, T, H, W, 3, device=frame_u8.device, dtype=torch.uint8)
+    out_ids = None if ids is None else torch.empty(B, T, H, W, device=frame_u8.device, dtype=torch.int32)
+    if B * T:
+        thr = float("-inf") if occ_threshold is None else float(occ_threshold)
+        _lib.check(_lib.lib().c2m_detail_warp(_p(frame_u8), _p(generated), _p(warped), _p(flow), _p(occ), _p(ids), thr,
+                                              int(fill_id), B, T, h, w, H, W, _p(out), _p(out_ids), _stream()), "detail_warp")
+    return out, out_ids
+
+
 # =============================================================================================== rendering (csrc/render.hip)
 def _sheet_plan(name, x, channels, size, dtypes=(torch.float32, torch.bfloat16)):
     """Checks of one [B,C,T,H,W] device tensor that becomes a sheet -> (B, C, T, H, W, rows, cols)."""

@@ -345,6 +345,20 @@ int c2m_label_warp(const float* flow, long sb, long sc, long st, const float* oc
                    const float* planes_f, int Cf, const int32_t* planes_i, int Ci, int B, int T, int H, int W, float* out_f,
                    int32_t* out_i, void* stream);
 
+/* ---- predicted frames at dataset resolution (detail_warp.hip): c2m_amd.fullres ---------------------------------------------
+ * The reference has no counterpart.  frame [B][H][W][3] uint8 is the last input frame at the output size; generated, warped
+ * [B][3][T][h][w], flow [B][2][T][h][w] (working-size pixels) and occ [B][1][T][h][w] (NULL: 1 everywhere) are dense fp32 at the
+ * working size, warped being the working-size frame moved by `flow` without occlusion (c2m_flow_warp_fwd).  With up() the
+ * bilinear enlargement (upsample_bilinear2d, align_corners=False) and warpF the bilinear value of `frame` at the position the
+ * working-size warp reads, mapped to the large grid and border-clamped (csrc/warp_coord.h, warp_source_at):
+ *     out [B][T][H][W][3] uint8 = floor(clip(255 up(generated) + up(occ) (warpF - 255 up(warped)), 0, 255) + 0.5), NaN -> 0.
+ * ids [B][H][W] int32 or NULL: out_ids [B][T][H][W] = the id at the nearest pixel of the same position (ties to even), fill_id
+ * where up(occ) < threshold (pass -inf for "never").  Needs 2 <= h <= H, 2 <= w <= W, H * W * 3 < 2^31.  One launch, no
+ * atomics, no workspace, bit-repeatable; offsets across frames are 64-bit.                                                  */
+int c2m_detail_warp(const uint8_t* frame, const float* generated, const float* warped, const float* flow, const float* occ,
+                    const int32_t* ids, float threshold, int fill_id, int B, int T, int h, int w, int H, int W, uint8_t* out,
+                    int32_t* out_ids, void* stream);
+
 /* ---- loss reductions (losses.hip) ---------------------------------------------------------------------------
  * losses/losses.py:180-189 L1MaskedLoss (also :60-65 VGG L1, model.py:118-121 feature matching); :152-177 SSIM. */
 int c2m_l1_mean_fwd(const void* a, const void* b, const float* mask, float* out, long total, int C, long inner,
