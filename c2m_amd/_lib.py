@@ -115,6 +115,8 @@ _SIGS = {
     "c2m_label_warp": (c_int, [c_void_p, c_long, c_long, c_long, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 +
                        [c_void_p] * 3),
     "c2m_detail_warp": (c_int, [c_void_p] * 6 + [c_float, c_int] + [c_int] * 6 + [c_void_p] * 3),
+    "c2m_frame_quality_workspace_bytes": (c_long, [c_int] * 4),
+    "c2m_frame_quality": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [c_double, c_void_p, c_long, c_void_p, c_void_p]),
     "c2m_render_frames": (c_int, [c_void_p, c_int] + [c_int] * 8 + [c_void_p, c_void_p]),
     "c2m_render_flow_workspace_bytes": (c_long, [c_int]),
     "c2m_render_flow": (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_void_p]),

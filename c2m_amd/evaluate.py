@@ -157,3 +157,127 @@ class DetectionScore:
             f.write(f"mse_traj_loss {r['mse_traj']}\n")
             f.write(f"mse_normalized_traj_loss {r['mse_normalized_traj']}\n\n\n")
         return r
+
+
+# ------------------------------------------------------------------------------------------ frame quality: PSNR and SSIM
+# What video-prediction work reports next to FID / FVD and what needs no weights: per-frame PSNR and SSIM against the real
+# future frames, for the whole frame and per region.
+QUALITY_REGIONS = ("foreground", "background", "guided", "disoccluded")
+_NAN = float("nan")
+
+
+def quality_regions(fg_mask, instance_mask, clicked_ids=None, occlusion=None, occ_threshold=0.5):
+    """The region bytes of frame_quality for the scored frames -> uint8 [B,T,H,W] on the inputs' device.
+    bit 0 foreground: any channel of fg_mask [B,9,T,H,W] (ground truth of the scored frames) is set; bit 1 background: the
+    rest; bit 2 guided: instance_mask [B,1,T,H,W] (or [B,T,H,W]) holds one of clicked_ids[b] (a list of ids per sample);
+    bit 3 disoccluded: occlusion [B,1,T,H,W] (the model's occlusion_bw) is below occ_threshold."""
+    if not isinstance(fg_mask, torch.Tensor) or fg_mask.dim() != 5:
+        raise ValueError("fg_mask must be [B,C,T,H,W]")
+    B, _, T, H, W = fg_mask.shape
+    inst = instance_mask[:, 0] if instance_mask.dim() == 5 else instance_mask
+    if tuple(inst.shape) != (B, T, H, W):
+        raise ValueError(f"instance_mask must be {(B, 1, T, H, W)} or {(B, T, H, W)}, got {tuple(instance_mask.shape)}")
+    fg = (fg_mask != 0).any(1)
+    bits = fg.to(torch.uint8) + (~fg).to(torch.uint8) * 2
+    if clicked_ids is not None:
+        if len(clicked_ids) != B:
+            raise ValueError(f"clicked_ids must hold one list of ids per sample ({B}), got {len(clicked_ids)}")
+        for b, ids in enumerate(clicked_ids):
+            ids = torch.as_tensor(ids).reshape(-1).tolist()
+            if ids:
+                pick = torch.isin(inst[b], torch.tensor(ids, dtype=inst.dtype, device=inst.device))
+                bits[b] += pick.to(torch.uint8) * 4
+    if occlusion is not None:
+        if tuple(occlusion.shape) != (B, 1, T, H, W):
+            raise ValueError(f"occlusion must be {(B, 1, T, H, W)}, got {tuple(occlusion.shape)}")
+        bits += (occlusion[:, 0] < occ_threshold).to(torch.uint8) * 8
+    return bits.contiguous()
+
+
+def _div(a, b):
+    """a / b, NaN where b is 0."""
+    return torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), torch.full_like(a, _NAN))
+
+
+def quality_from_sums(sums, channels, data_range, region_names=None):
+    """The host arithmetic of frame_quality: sums [B,T,9,4] float64 (n_pixels, sse, n_windows, ssim_sum) -> the result dict."""
+    sums = torch.as_tensor(sums, dtype=torch.float64)
+    n, sse, nw, ss = sums.unbind(-1)
+    L2 = float(data_range) ** 2
+    mse_raw = _div(sse, n * channels)
+    with_err = sse > 0
+    psnr = torch.where(with_err, 10.0 * torch.log10(L2 / torch.where(with_err, mse_raw, torch.ones_like(mse_raw))),
+                       torch.where(n > 0, torch.full_like(sse, float("inf")), torch.full_like(sse, _NAN)))
+    mse, ssim = mse_raw / L2, _div(ss, nw)
+    k = 8 if region_names is None else len(region_names)
+    if not 0 <= k <= 8:
+        raise ValueError("a region byte has 8 bits")
+    return {"mse": mse[..., 0], "psnr": psnr[..., 0], "ssim": ssim[..., 0], "region_mse": mse[..., 1:1 + k],
+            "region_psnr": psnr[..., 1:1 + k], "region_ssim": ssim[..., 1:1 + k], "region_pixels": n[..., 1:1 + k]}
+
+
+def frame_quality(pred, target, regions=None, region_names=None):
+    """PSNR and SSIM of every predicted frame against the real one (ops.frame_quality), on the host after one copy.
+    pred / target: float [B,C,T,H,W] in [0,1] (out["generated"] against video[:, :, t_in:]) or uint8 [B,T,H,W,C]
+    (fullres.upscale's frames against the dataset's); regions: quality_regions(...) or None.
+    Returns float64 tensors: mse (in units of L^2, so both forms agree), psnr (inf for identical frames), ssim [B,T];
+    region_mse, region_psnr, region_ssim, region_pixels [B,T,8] (or len(region_names)).  NaN where a region is empty (ssim:
+    where it holds no window centre)."""
+    sums = ops.frame_quality(pred, target, regions).cpu()                          # the one copy to the host
+    u8 = pred.dtype == torch.uint8
+    return quality_from_sums(sums, pred.shape[-1] if u8 else pred.shape[1], 255.0 if u8 else 1.0, region_names)
+
+
+class QualityScore:
+    """Means of frame_quality results over a dataset: overall and per predicted-frame index, whole frame and per region.
+    NaN entries (empty regions) are left out of their mean; inf PSNR entries (identical frames) are counted in
+    psnr_identical and not averaged."""
+    _KEYS = ("mse", "psnr", "ssim")
+
+    def __init__(self, region_names=QUALITY_REGIONS):
+        self.region_names = tuple(region_names)
+        self.rows = {k: [] for k in self._KEYS}              # each entry [B,T,1+R]: the frame, then the regions
+
+    def update(self, result):
+        R = len(self.region_names)
+        for k in self._KEYS:
+            whole, reg = torch.as_tensor(result[k], dtype=torch.float64), torch.as_tensor(result["region_" + k], dtype=torch.float64)
+            if reg.shape[-1] < R:
+                raise ValueError(f"result holds {reg.shape[-1]} regions, the score has {R}")
+            row = torch.cat([whole.unsqueeze(-1), reg[..., :R]], -1)
+            if self.rows[k] and row.shape[1] != self.rows[k][0].shape[1]:
+                raise ValueError("results with different numbers of predicted frames")
+            self.rows[k].append(row)
+
+    @staticmethod
+    def _mean(v, dim):
+        ok = torch.isfinite(v)
+        return _div(torch.where(ok, v, torch.zeros_like(v)).sum(dim), ok.sum(dim).double())
+
+    def result(self):
+        names = ("frame",) + self.region_names
+        out = {}
+        for k in self._KEYS:
+            v = torch.cat(self.rows[k], 0) if self.rows[k] else torch.zeros(0, 0, len(names), dtype=torch.float64)
+            overall, per_t = self._mean(v, (0, 1)), self._mean(v, 0)                  # [1+R], [T,1+R]
+            for i, name in enumerate(names):
+                key = k if i == 0 else f"{name}_{k}"
+                out[key] = float(overall[i])
+                out[key + "_per_frame"] = per_t[:, i].tolist()
+                if k == "psnr":
+                    out[key.replace("psnr", "psnr_identical")] = int(torch.isinf(v[..., i]).sum())
+        out["frames"] = int(sum(r.shape[0] * r.shape[1] for r in self.rows["mse"]))
+        return out
+
+    def write(self, path):
+        r = self.result()
+        with open(path, "a") as f:
+            f.write(f"frames {r['frames']}\n")
+            for name in ("",) + tuple(n + "_" for n in self.region_names):
+                f.write(f"{name}psnr {r[name + 'psnr']} {name}psnr_identical {r[name + 'psnr_identical']}\n")
+                f.write(f"{name}ssim {r[name + 'ssim']}\n")
+                f.write(f"{name}mse {r[name + 'mse']}\n")
+                for k in self._KEYS:
+                    f.write(f"{name}{k}_per_frame {' '.join(str(v) for v in r[name + k + '_per_frame'])}\n")
+            f.write("\n\n")
+        return r

@@ -2827,6 +2827,100 @@ def detail_warp(frame_u8, generated, warped, flow, occ=None, ids=None, occ_thres
     return out, out_ids
 
 
+# ====================================================================================== frame quality (csrc/quality.hip)
+QUALITY_TAPS = 11
+QUALITY_SIGMA = 1.5
+QUALITY_ROWS = 9            # the whole frame, then region bits 0..7
+
+
+def quality_weights():
+    """The eleven taps of the SSIM window, float64: exp(-i^2 / (2 sigma^2)), i = -5..5, normalised to sum 1."""
+    i = np.arange(QUALITY_TAPS, dtype=np.float64) - QUALITY_TAPS // 2
+    w = np.exp(-(i * i) / (2.0 * QUALITY_SIGMA * QUALITY_SIGMA))
+    return w / w.sum()
+
+
+_QUALITY_FLOATS = (torch.float32, torch.bfloat16)
+
+
+def _frame_quality_plan(pred, target, regions=None):
+    """Forms, dtypes and shapes of frame_quality, checked before anything is launched: (form, B, C, T, H, W) with form "float"
+    ([B,C,T,H,W] fp32 / bf16, L = 1) or "uint8" ([B,T,H,W,C], L = 255)."""
+    for name, t in (("pred", pred), ("target", target)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5:
+            raise ValueError(f"{name} must be a 5-d tensor: float [B,C,T,H,W] or uint8 [B,T,H,W,C]")
+        if t.dtype != torch.uint8 and t.dtype not in _QUALITY_FLOATS:
+            raise ValueError(f"{name} must be fp32, bf16 or uint8, got {t.dtype}")
+    if (pred.dtype == torch.uint8) != (target.dtype == torch.uint8):
+        raise ValueError(f"pred and target must have the same form (both float [B,C,T,H,W] or both uint8 [B,T,H,W,C]), got "
+                         f"{pred.dtype} and {target.dtype}")
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+    if pred.dtype == torch.uint8:
+        form, (B, T, H, W, C) = "uint8", pred.shape
+    else:
+        form, (B, C, T, H, W) = "float", pred.shape
+    if C not in (1, 3):
+        raise ValueError(f"{form} frames must have 1 or 3 channels, got {C} in {tuple(pred.shape)}")
+    if H < QUALITY_TAPS or W < QUALITY_TAPS:
+        raise ValueError(f"a frame must hold one {QUALITY_TAPS}x{QUALITY_TAPS} SSIM window, got {H}x{W}")
+    if H * W * C >= 2 ** 31:
+        raise ValueError(f"one {H}x{W}x{C} frame has 2^31 elements or more")
+    if regions is not None:
+        if not isinstance(regions, torch.Tensor) or regions.dtype != torch.uint8:
+            raise ValueError(f"regions must be a uint8 tensor, got {getattr(regions, 'dtype', type(regions).__name__)}")
+        if tuple(regions.shape) != (B, T, H, W):
+            raise ValueError(f"regions must be {(B, T, H, W)} for frames {tuple(pred.shape)}, got {tuple(regions.shape)}")
+    return form, B, C, T, H, W
+
+
+def _quality_operand(x, form, H, W, C):
+    """x with dense inner dims (a copy only if they are not) and its (B, C, T) strides in elements."""
+    s = x.stride()
+    if form == "uint8":
+        if s[2:] != (W * C, C, 1) or min(s[0], s[1]) < H * W * C:
+            x = x.contiguous()
+        return x, (x.stride(0), 0, x.stride(1))
+    if s[3:] != (W, 1) or min(s[:3]) < H * W:
+        x = x.contiguous()
+    return x, x.stride()[:3]
+
+
+def frame_quality(pred, target, regions=None):
+    """Per-frame squared error and SSIM sums of `pred` against `target`: float64 [B,T,9,4] on the device, row 0 the whole frame,
+    row 1 + k the pixels whose `regions` byte has bit k; columns (n_pixels, sse, n_windows, ssim_sum).
+
+    Both operands float [B,C,T,H,W] (fp32 or bf16, nominal range [0,1], L = 1, not clamped) or both uint8 [B,T,H,W,C] (L = 255,
+    on the integer levels); C 1 or 3; H, W >= 11.  B- and T-strided views (frames[:, t_in:], video[:, :, t_in:]) go in without a
+    copy.  regions: uint8 [B,T,H,W] or None.  sse counts every pixel; ssim_sum the centres whose 11x11 Gaussian window (sigma
+    1.5) lies inside the frame, SSIM as skimage's structural_similarity(gaussian_weights=True, use_sample_covariance=False)
+    computes it, in fp64.  Two launches, no atomics, bit-repeatable, no autograd."""
+    for t in (pred, target, regions):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    form, B, C, T, H, W = _frame_quality_plan(pred, target, regions)
+    for t in (pred, target, regions):
+        if t is not None and t.device.index != _cur_device():
+            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    pred, target = pred.detach(), target.detach()
+    if pred.dtype != target.dtype:                       # fp32 against bf16: bf16 -> fp32 is exact
+        pred, target = pred.float(), target.float()
+    pred, sp = _quality_operand(pred, form, H, W, C)
+    target, st = _quality_operand(target, form, H, W, C)
+    regions = None if regions is None else _f(regions)
+    out = torch.zeros(B, T, QUALITY_ROWS, 4, device=pred.device, dtype=torch.float64)
+    if B * T:
+        L = _lib.lib()
+        nbytes = L.c2m_frame_quality_workspace_bytes(B, T, H, W)
+        work = torch.empty(nbytes // 8, device=pred.device, dtype=torch.float64)
+        code = 2 if form == "uint8" else _dt(pred)
+        w = quality_weights()
+        _lib.check(L.c2m_frame_quality(_p(pred), _p(target), _p(regions), code, B, C, T, H, W, (ctypes.c_long * 3)(*sp),
+                                       (ctypes.c_long * 3)(*st), w.ctypes.data_as(ctypes.c_void_p),
+                                       255.0 if form == "uint8" else 1.0, _p(work), nbytes, _p(out), _stream()), "frame_quality")
+    return out
+
+
 # =============================================================================================== rendering (csrc/render.hip)
 def _sheet_plan(name, x, channels, size, dtypes=(torch.float32, torch.bfloat16)):
     """Checks of one [B,C,T,H,W] device tensor that becomes a sheet -> (B, C, T, H, W, rows, cols)."""

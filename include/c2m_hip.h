@@ -359,6 +359,23 @@ int c2m_detail_warp(const uint8_t* frame, const float* generated, const float* w
                     const int32_t* ids, float threshold, int fill_id, int B, int T, int h, int w, int H, int W, uint8_t* out,
                     int32_t* out_ids, void* stream);
 
+/* ---- frame quality (quality.hip): c2m_amd.evaluate.frame_quality ---------------------------------------------------------------
+ * The reference has no counterpart.  Scores B*T predicted frames against the real ones: out [B][T][9][4] float64, row 0 the whole
+ * frame and row 1 + k the pixels whose regions byte has bit k, columns (n_pixels, sse, n_windows, ssim_sum): sse the squared
+ * error summed over pixels and channels, n_windows the centres whose 11 x 11 window lies inside the frame (and, for a region,
+ * whose own pixel has the bit), ssim_sum the sum over those centres of the channel-mean SSIM (Wang et al. as skimage evaluates
+ * it with gaussian_weights=True, use_sample_covariance=False, data_range=L; C1 = (0.01 L)^2, C2 = (0.03 L)^2).
+ * form 0 / 1: fp32 / bf16 [B][C][T][H][W]; form 2: uint8 [B][T][H][W][C] (integer levels, pass L = 255).  C is 1 or 3, H and W
+ * at least 11.  pred_strides / target_strides: HOST arrays of the (B, C, T) strides in elements (C unused for form 2); rows, and
+ * for form 2 the channels, are dense.  regions [B][T][H][W] uint8, dense, or NULL (rows 1..8 are then zero).  weights: HOST
+ * array of the eleven normalised float64 taps.  workspace: c2m_frame_quality_workspace_bytes(B, T, H, W) bytes.
+ * Moments and everything after them are fp64; the uint8 squared error is summed in integers.  Two launches, no atomics,
+ * bit-repeatable.                                                                                                             */
+long c2m_frame_quality_workspace_bytes(int B, int T, int H, int W);
+int c2m_frame_quality(const void* pred, const void* target, const uint8_t* regions, int form, int B, int C, int T, int H, int W,
+                      const long* pred_strides, const long* target_strides, const double* weights, double L, void* workspace,
+                      long workspace_bytes, double* out, void* stream);
+
 /* ---- loss reductions (losses.hip) ---------------------------------------------------------------------------
  * losses/losses.py:180-189 L1MaskedLoss (also :60-65 VGG L1, model.py:118-121 feature matching); :152-177 SSIM. */
 int c2m_l1_mean_fwd(const void* a, const void* b, const float* mask, float* out, long total, int C, long inner,
