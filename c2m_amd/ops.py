@@ -3446,3 +3446,113 @@ def match_detections(dets, kept, index, roi, x, batch, scale, size):
                                                    0.005 * w * h, h * w * 0.01, _p(flags), _p(boxes), _p(err), _stream()),
                    "match_detections")
     return flags, boxes, err
+
+
+# =============================================================================================== Panoptic-DeepLab post-processing
+# (csrc/panoptic.hip; c2m_amd.segment is the public interface)
+PANOPTIC_MAX_TOP_K = 1024       # c2m_panoptic_max_top_k(): the grouping kernel stages a frame's centres whole in LDS
+_PanopticPlan = collections.namedtuple(
+    "_PanopticPlan", "form N C H W things threshold nms_kernel top_k label_divisor stuff_area ignore_label")
+_PANOPTIC_TABLES = {}
+
+
+def _panoptic_plan(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k):
+    """Every check of panoptic_maps, made before anything is launched (host tensors pass: the device is the launch path's
+    check).  semantic: fp32 logits [N,C,H,W] (form "logits") or uint8 / int64 labels [N,H,W] (form "labels")."""
+    for name, t in (("semantic", semantic), ("center", center), ("offset", offset)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+    if semantic.dim() == 4 and semantic.dtype == torch.float32:
+        form, (N, C, H, W) = "logits", semantic.shape
+        if not 1 <= C <= 256:
+            raise ValueError(f"semantic logits must have 1..256 classes (labels are uint8), got {C}")
+    elif semantic.dim() == 3 and semantic.dtype in (torch.uint8, torch.int64):
+        form, C, (N, H, W) = "labels", 256, semantic.shape
+    else:
+        raise ValueError("semantic must be fp32 logits [N,C,H,W] or uint8 / int64 labels [N,H,W], got "
+                         f"{semantic.dtype} {tuple(semantic.shape)}")
+    for name, t, ch in (("center", center, 1), ("offset", offset, 2)):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be fp32, got {t.dtype}")
+        if tuple(t.shape) != (N, ch, H, W):
+            raise ValueError(f"{name} must be {(N, ch, H, W)} for semantic {tuple(semantic.shape)}, got {tuple(t.shape)}")
+    for name, t in (("semantic", semantic), ("center", center), ("offset", offset)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.device != semantic.device:
+            raise ValueError(f"the heads must be on one device, got {semantic.device} and {t.device} ({name})")
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"a frame of {H}x{W} pixels is empty or too large (H * W must be below 2**31)")
+    try:
+        nms_kernel, top_k, label_divisor, stuff_area, ignore_label = (
+            int(v) for v in (nms_kernel, top_k, label_divisor, stuff_area, ignore_label))
+        threshold = float(threshold)
+        things = tuple(sorted(set(int(c) for c in thing_list)))
+    except (TypeError, ValueError):
+        raise ValueError("nms_kernel, top_k, label_divisor, stuff_area, ignore_label must be integers, threshold a number and "
+                         "thing_list a list of class ids") from None
+    if not (1 <= nms_kernel <= 15 and nms_kernel % 2 == 1):
+        raise ValueError(f"nms_kernel must be odd and in 1..15, got {nms_kernel}")
+    if top_k is None or not 1 <= top_k <= PANOPTIC_MAX_TOP_K:
+        raise ValueError(f"top_k is required and must be in 1..{PANOPTIC_MAX_TOP_K}, got {top_k}")
+    if not threshold >= 0:                      # a candidate's score is then positive: the radix select orders by the float bits
+        raise ValueError(f"threshold must be >= 0, got {threshold}")
+    hi = C - 1 if form == "logits" else 254
+    if any(not 0 <= c <= min(hi, 254) for c in things):
+        raise ValueError(f"thing_list must lie in 0..{min(hi, 254)} for this input, got {list(thing_list)}")
+    if label_divisor <= top_k:
+        raise ValueError(f"label_divisor={label_divisor} must be above top_k={top_k}: the instance number must fit below it")
+    if 256 * label_divisor >= 2 ** 31:
+        raise ValueError(f"label_divisor={label_divisor} is too large: class * label_divisor must stay below 2**31")
+    if not 0 <= ignore_label <= 255 or ignore_label in things:
+        raise ValueError(f"ignore_label must be in 0..255 and no thing class, got {ignore_label}")
+    return _PanopticPlan(form, N, C, H, W, things, threshold, nms_kernel, top_k, label_divisor, stuff_area, ignore_label)
+
+
+def _panoptic_tables(things, device):
+    """Device tables of a thing list: uint8 [256] (0: no thing, else 1 + position) and int32 [len] (the classes, ascending)."""
+    key = (things, device.index)
+    if key not in _PANOPTIC_TABLES:
+        tab = np.zeros(256, np.uint8)
+        for i, c in enumerate(things):
+            tab[c] = i + 1
+        _PANOPTIC_TABLES[key] = (torch.from_numpy(tab).to(device),
+                                 torch.tensor(list(things) or [0], dtype=torch.int32, device=device))
+    return _PANOPTIC_TABLES[key]
+
+
+def panoptic_maps(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k):
+    """Panoptic-DeepLab's post-processing for N frames in one call (csrc/panoptic.hip; the contract is in include/c2m_hip.h and
+    DESIGN.md 4.2i).  semantic: fp32 logits [N,C,H,W] or uint8 / int64 labels [N,H,W] with values in 0..255; center [N,1,H,W],
+    offset [N,2,H,W] (dy, dx) fp32.  Returns device tensors: semantic uint8, instance int32, panoptic int32 [N,H,W], centers
+    int32 [N,top_k,2] (y, x; zero past the count) and center_count int32 [N].  Six launches on the current stream; nothing is read
+    back and nothing synchronises."""
+    for t in (semantic, center, offset):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    pl = _panoptic_plan(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k)
+    if semantic.device.index != _cur_device():
+        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{semantic.device.index} but the current device is cuda:{_cur_device()}")
+    L = _lib.lib()
+    assert L.c2m_panoptic_max_top_k() == PANOPTIC_MAX_TOP_K
+    dev = semantic.device
+    semantic, center, offset = semantic.detach(), center.detach(), offset.detach()
+    logits = semantic if pl.form == "logits" else None
+    labels = None if pl.form == "logits" else (semantic if semantic.dtype == torch.uint8 else semantic.to(torch.uint8))
+    table, classes = _panoptic_tables(pl.things, dev)
+    N, H, W = pl.N, pl.H, pl.W
+    sem = torch.empty(N, H, W, device=dev, dtype=torch.uint8)
+    ins = torch.empty(N, H, W, device=dev, dtype=torch.int32)
+    pan = torch.empty(N, H, W, device=dev, dtype=torch.int32)
+    centers = torch.empty(N, pl.top_k, 2, device=dev, dtype=torch.int32)
+    count = torch.empty(N, device=dev, dtype=torch.int32)
+    if N:
+        nbytes = L.c2m_panoptic_workspace_bytes(N, H, W, pl.top_k, len(pl.things))
+        if nbytes < 0:
+            raise ValueError(f"panoptic_maps: sizes out of range (N={N}, {H}x{W}, top_k={pl.top_k})")
+        work = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+        _lib.check(L.c2m_panoptic_maps(_p(logits), _p(labels), pl.C, _p(center), _p(offset), _p(table), _p(classes),
+                                       len(pl.things), _p(sem), _p(ins), _p(pan), _p(centers), _p(count), _p(work), nbytes, N, H,
+                                       W, pl.threshold, pl.nms_kernel, pl.top_k, pl.label_divisor, pl.stuff_area,
+                                       pl.ignore_label, _stream()), "panoptic_maps")
+    return {"semantic": sem, "instance": ins, "panoptic": pan, "centers": centers, "center_count": count}

@@ -500,6 +500,34 @@ int c2m_instance_match(const int32_t* pairs, const int32_t* ref_slots, const int
                        const int32_t* frame_count, int32_t* link, int P, int max_nodes, int iou_num, int iou_den,
                        int same_class, void* stream);
 
+/* ---- Panoptic-DeepLab post-processing (panoptic.hip; c2m_amd.segment) --------------------------------------------------------
+ * The label maps and instance maps of N images from the network's three heads, as the reference's get_panoptic_segmentation
+ * (post_processing/instance_post_processing.py) and the instance-id image of generate_segmentation.py:299-305 compute them for
+ * one image at a time.  Exactly one of logits [N][C][H][W] fp32 (1 <= C <= 256; labels = argmax, first maximum) and labels
+ * [N][H][W] uint8 is non-NULL.  center [N][1][H][W], offset [N][2][H][W] (dy, dx) fp32.  class_table: device uint8 [256], 0 for a
+ * class that is no thing, else 1 + its position in thing_classes (device int32 [n_things], ascending; n_things <= 255).
+ *   centres   score > threshold (>= 0; strict) and equal to the maximum of its nms_kernel x nms_kernel window (odd, 1..15; positions
+ *             outside the image do not take part; a plateau keeps all its pixels).  With top_k or more candidates only those
+ *             strictly above the top_k-th largest score remain (ties at that score all drop out).  Row-major order:
+ *             centers [N][top_k][2] (y, x), zero past center_count [N].  top_k <= c2m_panoptic_max_top_k() (1024).
+ *   grouping  a thing pixel belongs to the centre nearest to (y + dy, x + dx), squared distance in fp32, the first of equally
+ *             near ones; no centre: no pixel is claimed.
+ *   merge     centres ascending: class = the most frequent label among its pixels (ties: the smaller class), value
+ *             class * label_divisor + n, n = 1, 2, ... per class; a centre without pixels uses no number.  A class that is no
+ *             thing and holds >= stuff_area pixels keeps class * label_divisor; everything else is ignore_label * label_divisor.
+ * Outputs [N][H][W]: semantic uint8, panoptic int32, instance int32 (the panoptic value on things, else panoptic / label_divisor).
+ * label_divisor > top_k, 256 * label_divisor < 2^31, 0 <= ignore_label <= 255, H * W < 2^31; index arithmetic over N*C*H*W is
+ * 64-bit.  workspace: c2m_panoptic_workspace_bytes(N, H, W, top_k, n_things) bytes (-1 for sizes out of range), int32-aligned.
+ * Everything is checked before the first launch; five kernels and a zero-fill on `stream`, no synchronisation, no copy to the host.
+ * int32 atomics only: bit-repeatable, and the centre order does not depend on scheduling.                                     */
+int c2m_panoptic_max_top_k(void);
+long c2m_panoptic_workspace_bytes(int N, int H, int W, int top_k, int n_things);
+int c2m_panoptic_maps(const float* logits, const uint8_t* labels, int C, const float* center, const float* offset,
+                      const uint8_t* class_table, const int32_t* thing_classes, int n_things, uint8_t* semantic,
+                      int32_t* instance, int32_t* panoptic, int32_t* centers, int32_t* center_count, void* workspace,
+                      long workspace_bytes, int N, int H, int W, float threshold, int nms_kernel, int top_k, int label_divisor,
+                      int stuff_area, int ignore_label, void* stream);
+
 /* ---- rendering (render.hip): results as uint8 pictures on the device ------------------------------------------------
  * A SHEET is uint8 [T][rows*H][cols*W][C] (HWC); sample b sits in cell (b / cols, b % cols), as the reference's merge
  * (utils/utils.py:26-43) lays samples out; cells without a sample hold zero input.  B <= rows * cols.  Inputs are dense
