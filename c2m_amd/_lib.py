@@ -78,6 +78,8 @@ _SIGS = {
     "c2m_panoptic_workspace_bytes": (c_long, [c_int] * 5),
     "c2m_panoptic_maps": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_long] + [c_int] * 3 +
                           [c_float] + [c_int] * 5 + [c_void_p]),
+    "c2m_map_quality_workspace_bytes": (c_long, [c_int] * 4),
+    "c2m_map_quality": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_long] + [c_int] * 7 + [c_void_p]),
     "c2m_event_create": (c_int, [c_void_p]),
     "c2m_event_record": (c_int, [c_void_p, c_void_p]),
     "c2m_event_elapsed_ms": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -25,6 +25,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_nc8.hip": NOSLP, "conv_wino.hip": NOSL
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
            "panoptic.hip": ["-ffp-contract=off"] + NOSLP,
+           "map_quality.hip": ["-ffp-contract=off"] + NOSLP,
            "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],
            "render.hip": ["-ffp-contract=off"] + NOSLP, "detect.hip": ["-ffp-contract=off"] + NOSLP,
            "flownet_ops.hip": ["-ffp-contract=off"] + NOSLP, "gnn.hip": ["-ffp-contract=off"] + NOSLP}

@@ -9,9 +9,10 @@ object; candidates with equal scores keep their box order; a non-finite head box
 import statistics
 import warnings
 
+import numpy as np
 import torch
 
-from . import ops
+from . import ops, segment
 from .modules.networks.yolo_v3 import Darknet
 
 _GRAPH_FIELDS = ("target_frames_nodes_roi", "x", "batch")
@@ -279,5 +280,175 @@ class QualityScore:
                 f.write(f"{name}mse {r[name + 'mse']}\n")
                 for k in self._KEYS:
                     f.write(f"{name}{k}_per_frame {' '.join(str(v) for v in r[name + k + '_per_frame'])}\n")
+            f.write("\n\n")
+        return r
+
+
+# ------------------------------------------------------------------------------------------ map quality: mIoU and panoptic quality
+# What future-segmentation work reports and what needs no weights either: the label maps a prediction carries forward (or the
+# segmenter's maps of predicted frames) against the maps of the real future frames.
+MAP_QUALITY = dict(num_classes=19, thing_list=segment.CITYSCAPES["thing_list"], label_divisor=segment.CITYSCAPES["label_divisor"],
+                   ignore_label=segment.CITYSCAPES["ignore_label"], max_pairs=65536)
+_PQ_GROUPS = (("All", None), ("Things", True), ("Stuff", False))
+
+
+def _map_params(who, params):
+    unknown = set(params) - set(MAP_QUALITY)
+    if unknown:
+        raise TypeError(f"{who} got unknown parameter(s) {sorted(unknown)}; known: {sorted(MAP_QUALITY)}")
+    return {**MAP_QUALITY, **params}
+
+
+def map_quality(pred_maps, gt_maps, **params):
+    """Panoptic-quality counts and the confusion matrix of every predicted map against the real one (ops.map_quality), on the
+    device, per frame.  pred_maps / gt_maps: int32 or uint8 [B,T,H,W], [B,1,T,H,W] or [N,H,W], of one dtype and, the channel
+    axis of the 5-D form aside, one shape (a rollout's [B,1,T,H,W] maps are scored against clip_maps' [B,T,H,W] as they are): the
+    instance-id image (things class * label_divisor + k, stuff the class, void ignore_label: r["instance_mask"] of a rollout,
+    segment.clip_maps), the `panoptic` map of segment.panoptic_maps (void ignore_label * label_divisor) or a plain label map.
+    Keyword parameters default to MAP_QUALITY: num_classes, thing_list, label_divisor, ignore_label (segment.CITYSCAPES) and
+    max_pairs, the slots of a frame's pair table (a power of two).
+    Returns a dict of device tensors with the leading axes [...] of the input ([B,T] or [N]): tp, fp, fn int32 [...,C]; iou
+    float64 [...,C], the sum of the matched IoUs; confusion int64 [...,C+1,C+1] ([pred, gt], void last); overflow bool [...]:
+    the frame had more distinct segment pairs than max_pairs and its counts are incomplete (MapScore.update refuses it)."""
+    p = _map_params("map_quality", params)
+    for name, t in (("pred_maps", pred_maps), ("gt_maps", gt_maps)):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (3, 4, 5) or (t.dim() == 5 and t.shape[1] != 1):
+            raise ValueError(f"{name} must be [B,T,H,W], [B,1,T,H,W] or [N,H,W], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    pred, gt = (t[:, 0] if t.dim() == 5 else t for t in (pred_maps, gt_maps))      # [B,1,T,H,W] and [B,T,H,W] are one clip
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred_maps {tuple(pred_maps.shape)} and gt_maps {tuple(gt_maps.shape)} differ in shape")
+    lead = tuple(pred.shape[:-2])
+    H, W = pred.shape[-2:]
+    m = ops.map_quality(pred.reshape(-1, H, W).contiguous(), gt.reshape(-1, H, W).contiguous(), **p)
+    return {k: v.view(*lead, *v.shape[1:]) for k, v in m.items()}
+
+
+def pq_average(tp, fp, fn, iou, classes):
+    """PQStat.pq_average over `classes`: ({"pq", "sq", "rq", "n"}, {class: {"pq", "sq", "rq"}}).  Classes with tp + fp + fn == 0
+    do not count.  With no counted class the reference divides by zero; here the averages are 0.0 and n is 0."""
+    pq = sq = rq = n = 0
+    per_class = {}
+    for c in classes:
+        t, p, f, i = int(tp[c]), int(fp[c]), int(fn[c]), float(iou[c])
+        if t + p + f == 0:
+            per_class[c] = {"pq": 0.0, "sq": 0.0, "rq": 0.0}
+            continue
+        n += 1
+        pq_c = i / (t + 0.5 * p + 0.5 * f)
+        sq_c = i / t if t != 0 else 0
+        rq_c = t / (t + 0.5 * p + 0.5 * f)
+        per_class[c] = {"pq": pq_c, "sq": sq_c, "rq": rq_c}
+        pq += pq_c
+        sq += sq_c
+        rq += rq_c
+    if n == 0:
+        return {"pq": 0.0, "sq": 0.0, "rq": 0.0, "n": 0}, per_class
+    return {"pq": pq / n, "sq": sq / n, "rq": rq / n, "n": n}, per_class
+
+
+def semantic_scores(confusion):
+    """SemanticEvaluator.evaluate on a [C+1,C+1] confusion matrix ([pred, gt], void last), restated as it is -- the IoU of a
+    class is assigned under acc_valid (the class has ground-truth pixels), the mean divides by the classes of iou_valid."""
+    conf = np.asarray(confusion, dtype=np.int64)
+    C = conf.shape[0] - 1
+    acc, iou = np.zeros(C, dtype=np.float64), np.zeros(C, dtype=np.float64)
+    tp = conf.diagonal()[:-1].astype(np.float64)
+    pos_gt = np.sum(conf[:-1, :-1], axis=0).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        class_weights = pos_gt / np.sum(pos_gt)
+        pos_pred = np.sum(conf[:-1, :-1], axis=1).astype(np.float64)
+        acc_valid = pos_gt > 0
+        acc[acc_valid] = tp[acc_valid] / pos_gt[acc_valid]
+        iou_valid = (pos_gt + pos_pred) > 0
+        union = pos_gt + pos_pred - tp
+        iou[acc_valid] = tp[acc_valid] / union[acc_valid]
+        macc = np.sum(acc) / np.sum(acc_valid)
+        miou = np.sum(iou) / np.sum(iou_valid)
+        fiou = np.sum(iou * class_weights)
+        pacc = np.sum(tp) / np.sum(pos_gt)
+    return {"mIoU": float(100 * miou), "fwIoU": float(100 * fiou), "mACC": float(100 * macc), "pACC": float(100 * pacc)}
+
+
+class MapScore:
+    """Sums of map_quality results over a dataset and the reference's averages of them (cityscapesscripts' PQStat.pq_average /
+    average_pq and Panoptic-DeepLab's SemanticEvaluator.evaluate): overall and, where the results had a frame axis [B,T], per
+    predicted-frame index.  The per-frame values are added in the order they arrive."""
+
+    def __init__(self, **params):
+        p = _map_params("MapScore", params)
+        self.num_classes, self.max_pairs = int(p["num_classes"]), int(p["max_pairs"])
+        self.things = tuple(sorted(set(int(c) for c in p["thing_list"])))
+        self.params = p
+        self.per_t = None                                    # None until the first update; [] for results without a frame axis
+        self.total = self._zero()
+        self.frames = 0
+
+    def _zero(self):
+        C = self.num_classes
+        return {"tp": np.zeros(C, np.int64), "fp": np.zeros(C, np.int64), "fn": np.zeros(C, np.int64),
+                "iou": np.zeros(C, np.float64), "confusion": np.zeros((C + 1, C + 1), np.int64)}
+
+    @staticmethod
+    def _add(acc, row):
+        for k in acc:
+            acc[k] += row[k]                                 # iou: one float64 addition per class and frame, in arrival order
+
+    def update(self, result):
+        C = self.num_classes
+        host = {k: (result[k].cpu().numpy() if isinstance(result[k], torch.Tensor) else np.asarray(result[k]))
+                for k in ("tp", "fp", "fn", "iou", "confusion", "overflow")}
+        over = host.pop("overflow").astype(bool)
+        if over.any():
+            raise ValueError(f"{int(over.sum())} frame(s) had more distinct segment pairs than max_pairs={self.max_pairs}: "
+                             f"their counts are incomplete; call map_quality with a larger max_pairs")
+        lead = host["tp"].shape[:-1]
+        if host["tp"].shape[-1] != C or host["confusion"].shape[-2:] != (C + 1, C + 1) or len(lead) not in (1, 2):
+            raise ValueError(f"result of {host['tp'].shape[-1]} classes with leading axes {lead}; the score has {C} classes and "
+                             "takes [B,T] or [N] results")
+        T = lead[1] if len(lead) == 2 else 0
+        if self.per_t is None:
+            self.per_t = [self._zero() for _ in range(T)]
+        if len(self.per_t) != T:
+            raise ValueError("results with different numbers of predicted frames")
+        rows = {k: v.reshape((-1,) + v.shape[len(lead):]) for k, v in host.items()}
+        rows["iou"] = rows["iou"].astype(np.float64)
+        for i in range(rows["tp"].shape[0]):
+            row = {k: v[i] for k, v in rows.items()}
+            self._add(self.total, row)
+            if T:
+                self._add(self.per_t[i % T], row)
+            self.frames += 1
+
+    def _scores(self, acc):
+        out = {}
+        for name, isthing in _PQ_GROUPS:
+            classes = [c for c in range(self.num_classes) if isthing is None or (c in self.things) == isthing]
+            out[name], per_class = pq_average(acc["tp"], acc["fp"], acc["fn"], acc["iou"], classes)
+            if name == "All":
+                out["per_class"] = per_class
+        out.update(semantic_scores(acc["confusion"]))
+        return out
+
+    def result(self):
+        out = self._scores(self.total)
+        out["frames"] = self.frames
+        if self.per_t:
+            out["per_frame"] = [self._scores(a) for a in self.per_t]
+        return out
+
+    def write(self, path):
+        r = self.result()
+        rows = [("", r)] + [(f"frame{t}_", f) for t, f in enumerate(r.get("per_frame", ()))]
+        with open(path, "a") as f:
+            f.write(f"frames {r['frames']}\n")
+            for prefix, s in rows:
+                for name, _ in _PQ_GROUPS:
+                    g = s[name]
+                    f.write(f"{prefix}{name} pq {g['pq']} sq {g['sq']} rq {g['rq']} n {g['n']}\n")
+                for k in ("mIoU", "fwIoU", "mACC", "pACC"):
+                    f.write(f"{prefix}{k} {s[k]}\n")
+            for c, g in sorted(r["per_class"].items()):
+                f.write(f"class {c} pq {g['pq']} sq {g['sq']} rq {g['rq']}\n")
             f.write("\n\n")
         return r

@@ -3556,3 +3556,82 @@ def panoptic_maps(semantic, center, offset, thing_list, label_divisor, stuff_are
                                        W, pl.threshold, pl.nms_kernel, pl.top_k, pl.label_divisor, pl.stuff_area,
                                        pl.ignore_label, _stream()), "panoptic_maps")
     return {"semantic": sem, "instance": ins, "panoptic": pan, "centers": centers, "center_count": count}
+
+
+# ------------------------------------------------------------------------------------------ scoring of label maps
+# (csrc/map_quality.hip; c2m_amd.evaluate.map_quality is the public interface)
+MAP_QUALITY_MAX_KEYS = 1 << 20      # num_classes * label_divisor: the per-image tables are addressed by class * divisor + n
+MAP_QUALITY_MAX_PAIRS = 1 << 22
+_MapQualityPlan = collections.namedtuple("_MapQualityPlan", "N H W u8 num_classes things label_divisor ignore_label max_pairs")
+
+
+def _map_quality_plan(pred, gt, num_classes, thing_list, label_divisor, ignore_label, max_pairs):
+    """Every check of map_quality, made before anything is launched (host tensors pass: the device is the launch path's
+    check).  pred, gt: [N,H,W], both int32 or both uint8 -- no other dtype, so a negative value can only be an int32 the
+    kernel reads as void."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.int32, torch.uint8):
+            raise ValueError(f"{name} must be an int32 or uint8 label map, got {t.dtype}")
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be [N,H,W], got {tuple(t.shape)}")
+    if pred.dtype != gt.dtype:
+        raise ValueError(f"pred and gt must have one dtype, got {pred.dtype} and {gt.dtype}")
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if pred.device != gt.device:
+        raise ValueError(f"pred and gt must be on one device, got {pred.device} and {gt.device}")
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise ValueError("pred and gt must be contiguous")
+    N, H, W = pred.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31 or N >= 2 ** 24:
+        raise ValueError(f"{N} frames of {H}x{W} pixels: a frame is empty or too large (H * W must be below 2**31)")
+    try:
+        num_classes, label_divisor, ignore_label, max_pairs = (int(v) for v in (num_classes, label_divisor, ignore_label, max_pairs))
+        things = tuple(sorted(set(int(c) for c in thing_list)))
+    except (TypeError, ValueError):
+        raise ValueError("num_classes, label_divisor, ignore_label and max_pairs must be integers and thing_list a list of "
+                         "class ids") from None
+    if not 1 <= num_classes <= 255:
+        raise ValueError(f"num_classes must be in 1..255, got {num_classes}")
+    if label_divisor < 1 or num_classes * label_divisor > MAP_QUALITY_MAX_KEYS:
+        raise ValueError(f"label_divisor={label_divisor} is out of range: it must be at least 1 and num_classes * label_divisor "
+                         f"at most {MAP_QUALITY_MAX_KEYS}")
+    if max_pairs < 1 or max_pairs > MAP_QUALITY_MAX_PAIRS or max_pairs & (max_pairs - 1):
+        raise ValueError(f"max_pairs must be a power of two in 1..{MAP_QUALITY_MAX_PAIRS}, got {max_pairs}")
+    if ignore_label < 0 or ignore_label >= 2 ** 31:
+        raise ValueError(f"ignore_label must be in 0..2**31-1, got {ignore_label}")
+    if any(not 0 <= c < num_classes for c in things) or ignore_label in things:
+        raise ValueError(f"thing_list must lie in 0..{num_classes - 1} and leave out ignore_label, got {list(thing_list)}")
+    return _MapQualityPlan(N, H, W, pred.dtype == torch.uint8, num_classes, things, label_divisor, ignore_label, max_pairs)
+
+
+def map_quality(pred, gt, num_classes, thing_list, label_divisor, ignore_label, max_pairs):
+    """Panoptic-quality counts and the confusion matrix of N predicted label maps against N ground-truth ones, per frame
+    (csrc/map_quality.hip; the contract is in include/c2m_hip.h and DESIGN.md 4.2j).  pred, gt: int32 or uint8 [N,H,W].
+    Returns device tensors: tp, fp, fn int32 [N,C], iou float64 [N,C], confusion int64 [N,C+1,C+1] ([pred, gt], void last),
+    overflow bool [N].  A zero-fill and three launches on the current stream; nothing is read back and nothing synchronises."""
+    pl = _map_quality_plan(pred, gt, num_classes, thing_list, label_divisor, ignore_label, max_pairs)
+    if not (pred.is_cuda and gt.is_cuda):
+        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    if pred.device.index != _cur_device():
+        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{pred.device.index} but the current device is cuda:{_cur_device()}")
+    L = _lib.lib()
+    dev, N, C = pred.device, pl.N, pl.num_classes
+    pred, gt = pred.detach(), gt.detach()
+    table, _ = _panoptic_tables(pl.things, dev)
+    tp, fp, fn = (torch.zeros(N, C, device=dev, dtype=torch.int32) for _ in range(3))
+    iou = torch.zeros(N, C, device=dev, dtype=torch.float64)
+    conf = torch.zeros(N, C + 1, C + 1, device=dev, dtype=torch.int64)
+    over = torch.zeros(N, device=dev, dtype=torch.uint8)
+    if N:
+        nbytes = L.c2m_map_quality_workspace_bytes(N, C, pl.label_divisor, pl.max_pairs)
+        if nbytes < 0:
+            raise ValueError(f"map_quality: sizes out of range (N={N}, num_classes={C}, label_divisor={pl.label_divisor}, "
+                             f"max_pairs={pl.max_pairs})")
+        work = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.int64)
+        _lib.check(L.c2m_map_quality(_p(pred), _p(gt), int(pl.u8), _p(table), _p(tp), _p(fp), _p(fn), _p(iou), _p(conf),
+                                     _p(over), _p(work), nbytes, N, pl.H, pl.W, C, pl.label_divisor, pl.ignore_label,
+                                     pl.max_pairs, _stream()), "map_quality")
+    return {"tp": tp, "fp": fp, "fn": fn, "iou": iou, "confusion": conf, "overflow": over.view(torch.bool)}

@@ -528,6 +528,31 @@ int c2m_panoptic_maps(const float* logits, const uint8_t* labels, int C, const f
                       long workspace_bytes, int N, int H, int W, float threshold, int nms_kernel, int top_k, int label_divisor,
                       int stuff_area, int ignore_label, void* stream);
 
+/* ---- Scoring of label maps (map_quality.hip; c2m_amd.evaluate.map_quality) ------------------------------------------------------
+ * Panoptic-quality counts and the confusion matrix of N predicted maps against N ground-truth maps, per image, as the reference's
+ * pq_compute_single_core (cityscapesscripts/evaluation/evalPanopticSemanticLabeling.py) and SemanticEvaluator.update compute them
+ * for one image at a time.  pred, gt: [N][H][W], both int32 or both uint8 (is_u8).  A value v reads as (cat, n) = (v, 0) below
+ * label_divisor, else (v / label_divisor, v % label_divisor); void: v < 0, cat == ignore_label or cat >= num_classes.  A segment
+ * is the pixels of one image with the same non-void (cat, n); a ground-truth segment of a thing class (thing_table: device uint8
+ * [256], non-zero for a thing) with n == 0 is a crowd region.
+ *   pairs     a non-crowd ground-truth segment g and a predicted segment p of the same class match iff 2 * inter > union, union =
+ *             area_p + area_g - inter - void_p (void_p: p's pixels on ground-truth void); a match adds 1 to tp[class] and
+ *             inter / union (float64) to iou[class], summed per class over g in ascending n.
+ *   fn        unmatched non-crowd ground-truth segments; fp: unmatched predicted segments unless 2 * (void_p + crowd_p) > area_p
+ *             (crowd_p: p's pixels on the crowd region of its own class).
+ *   confusion [N][C+1][C+1] int64, [pred][gt], void last.
+ * Outputs: tp, fp, fn int32 [N][C], iou float64 [N][C], confusion, overflow uint8 [N] (1: the image had more distinct pairs of
+ * equal class than max_pairs, the hash table's slots; the surplus pairs were dropped).  1 <= num_classes <= 255, label_divisor
+ * >= 1, num_classes * label_divisor <= 2^20, max_pairs a power of two <= 2^22, ignore_label >= 0, H * W < 2^31; the image offset
+ * is 64-bit.  workspace: c2m_map_quality_workspace_bytes(N, num_classes, label_divisor, max_pairs) bytes (-1 for sizes out of
+ * range), 8-byte aligned, zero-filled by the call.  Everything is checked before the first launch; a zero-fill and three kernels on
+ * `stream`, no synchronisation, no copy to the host, no loop that waits for another wave (the hash makes at most max_pairs probes).
+ * Integer atomics only: every output is bit-repeatable.                                                                        */
+long c2m_map_quality_workspace_bytes(int N, int num_classes, int label_divisor, int max_pairs);
+int c2m_map_quality(const void* pred, const void* gt, int is_u8, const uint8_t* thing_table, int32_t* tp, int32_t* fp,
+                    int32_t* fn, double* iou, int64_t* confusion, uint8_t* overflow, void* workspace, long workspace_bytes,
+                    int N, int H, int W, int num_classes, int label_divisor, int ignore_label, int max_pairs, void* stream);
+
 /* ---- rendering (render.hip): results as uint8 pictures on the device ------------------------------------------------
  * A SHEET is uint8 [T][rows*H][cols*W][C] (HWC); sample b sits in cell (b / cols, b % cols), as the reference's merge
  * (utils/utils.py:26-43) lays samples out; cells without a sample hold zero input.  B <= rows * cols.  Inputs are dense
