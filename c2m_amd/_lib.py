@@ -1,5 +1,5 @@
-"""ctypes binding of libc2m_hip.so (include/c2m_hip.h).  There is NO fallback: if the library is missing or a tensor
-is not on a HIP device, the op raises -- the product path never silently runs anything else."""
+"""ctypes binding of libc2m_hip.so; the signatures are parsed from include/c2m_hip.h.  There is NO fallback: if the
+library is missing or a tensor is not on a HIP device, the op raises -- the product path never silently runs anything else."""
 import ctypes
 import os
 import re
@@ -9,132 +9,42 @@ LIB_PATH = os.environ.get("C2M_AMD_LIB") or os.path.join(_HERE, "lib", "libc2m_h
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "c2m_hip.h")
 _lib = None
 
-c_void_p, c_int, c_long, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
+# by-value parameter types a prototype may use; every pointer is a c_void_p (device addresses, ctypes arrays, None)
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long": ctypes.c_long, "float": ctypes.c_float,
+            "double": ctypes.c_double, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8}
 
-_SIGS = {
-    "c2m_abi_version": (c_int, []),
-    "c2m_geom_len": (c_int, []),
-    "c2m_wino_geom_len": (c_int, []),
-    "c2m_conv_igemm": (c_int, [c_void_p] * 7 + [c_int, c_float, c_void_p]),
-    "c2m_nchw_to_nc8": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_void_p]),
-    "c2m_conv_patch_nc8": (c_int, [c_void_p] * 6 + [c_int, c_float, c_void_p]),
-    "c2m_conv_s2_nc8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "c2m_conv3d_nc8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "c2m_conv3d_dgrad_nc8": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "c2m_conv_wgrad3d_nc8": (c_int, [c_void_p] * 5 + [c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "c2m_conv_s2_dgrad_nc8": (c_int, [c_void_p] * 3 + [c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "c2m_pack_weights_bf16_s2_bytes": (c_long, [c_int, c_int]),
-    "c2m_conv_wgrad_nc8_splits": (c_int, [c_int, c_int, c_long, c_int, c_int, c_int]),
-    "c2m_conv_wgrad_nc8_slab_floats": (c_long, [c_int, c_int, c_long, c_int, c_int, c_int]),
-    "c2m_conv_wgrad_nc8": (c_int, [c_void_p] * 5 + [c_int, c_int, c_long, c_int, c_int, c_int, c_int, c_void_p]),
-    "c2m_reflect_border_add": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 7 + [c_void_p]),
-    "c2m_conv_igemm_splits": (c_int, [c_int, c_int, c_int]),
-    "c2m_splitk_reduce": (c_int, [c_void_p] * 3 + [c_long, c_int, c_long, c_int, c_int, c_float, c_int, c_void_p]),
-    "c2m_conv_wgrad_splits": (c_int, [c_int, c_int, c_int]),
-    "c2m_conv_wgrad_rows": (c_int, [c_int, c_int]),
-    "c2m_conv_wgrad": (c_int, [c_void_p] * 8),
-    "c2m_reflect_fold": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 7 + [c_void_p]),
-    "c2m_pack_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "c2m_pack_job_bytes": (c_int, []),
-    "c2m_pack_job_fill": (c_long, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_uint]),
-    "c2m_pack_multi": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p]),
-    "c2m_pack_weights_bf16_patch_bytes": (c_long, [c_int, c_int]),
-    "c2m_pack_weights_bf16_patch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "c2m_pack_weights_bf16_gather_bytes": (c_long, [c_void_p]),
-    "c2m_pack_weights_bf16_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "c2m_wino_upack_floats": (c_long, [c_int, c_int]),
-    "c2m_wino_filter_transform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "c2m_conv_wino": (c_int, [c_void_p] * 6 + [c_int, c_float, c_void_p]),
-    "c2m_wino_regions": (c_int, [c_int, c_int]),
-    "c2m_wino4_upack_floats": (c_long, [c_int, c_int]),
-    "c2m_wino4_filter_transform": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "c2m_wino4_regions": (c_int, [c_int, c_int]),
-    "c2m_conv_wino4": (c_int, [c_void_p] * 6 + [c_int, c_float, c_void_p]),
-    "c2m_ring_pack_floats": (c_long, [c_int, c_int]),
-    "c2m_ring_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "c2m_reflect_ring_dgrad": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "c2m_reflect_ring_buffer": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
-    "c2m_wino_wgrad_splits": (c_int, [c_int] * 5),
-    "c2m_conv_wino_wgrad": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
-    "c2m_conv_wino_wgrad3d": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
-    "c2m_prep_video": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
-    "c2m_prep_seg_onehot": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
-    "c2m_prep_flow_occ": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
-    "c2m_resize_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p]),
-    "c2m_resize_nearest": (c_int, [c_void_p, c_void_p, c_int, c_long] + [c_int] * 4 + [c_void_p] * 5),
-    "c2m_resize_flow": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 4 + [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int, c_void_p]),
-    "c2m_detect_input": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_long] * 4 + [c_int, c_int, c_void_p]),
-    "c2m_yolo_candidates": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float, c_int] + [c_void_p] * 5),
-    "c2m_nms_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
-    "c2m_match_detections": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-                                     c_void_p, c_long, c_int, c_int, c_int, c_double, c_double] + [c_void_p] * 4),
-    "c2m_instance_stats": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
-    "c2m_instance_compact": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
-    "c2m_instance_link_max_nodes": (c_int, []),
-    "c2m_instance_slots": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "c2m_instance_overlap": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
-    "c2m_instance_match": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
-    "c2m_panoptic_max_top_k": (c_int, []),
-    "c2m_panoptic_workspace_bytes": (c_long, [c_int] * 5),
-    "c2m_panoptic_maps": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 6 + [c_long] + [c_int] * 3 +
-                          [c_float] + [c_int] * 5 + [c_void_p]),
-    "c2m_map_quality_workspace_bytes": (c_long, [c_int] * 4),
-    "c2m_map_quality": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 8 + [c_long] + [c_int] * 7 + [c_void_p]),
-    "c2m_event_create": (c_int, [c_void_p]),
-    "c2m_event_record": (c_int, [c_void_p, c_void_p]),
-    "c2m_event_elapsed_ms": (c_int, [c_void_p, c_void_p, c_void_p]),
-    "c2m_event_destroy": (c_int, [c_void_p]),
-    "c2m_adam_chunk": (c_int, []),
-    "c2m_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_double] * 5 + [c_void_p]),
-    "c2m_norm_workspace_floats": (c_long, [c_int, c_int, c_long]),
-    "c2m_norm_stats": (c_int, [c_void_p] * 6 + [c_int, c_int, c_long, c_int, c_float, c_float, c_int, c_void_p]),
-    "c2m_norm_fwd": (c_int, [c_void_p] * 10 + [c_int, c_int, c_long, c_int, c_float, c_float, c_int, c_float, c_int, c_void_p]),
-    "c2m_norm_set_fused": (c_int, [c_int]),
-    "c2m_norm_apply": (c_int, [c_void_p] * 8 + [c_int, c_int, c_long, c_int, c_int, c_float, c_int, c_void_p]),
-    "c2m_norm_bwd": (c_int, [c_void_p] * 13 + [c_int, c_int, c_long, c_int, c_int, c_float, c_int, c_void_p]),
-    "c2m_act_bwd": (c_int, [c_void_p] * 3 + [c_long, c_int, c_float, c_int, c_void_p]),
-    "c2m_grad_to_nc8": (c_int, [c_int] + [c_void_p] * 5 + [c_long, c_int, c_long, c_long, c_int, c_float, c_void_p]),
-    "c2m_resample2d_fwd": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
-    "c2m_channelnorm_fwd": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p]),
-    "c2m_correlation_out_size": (c_int, [c_int] * 5),
-    "c2m_correlation_fwd": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_void_p]),
-    "c2m_bias_act": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_int, c_float, c_void_p]),
-    "c2m_flow_warp_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_void_p]),
-    "c2m_flow_warp_bwd_workspace_bytes": (c_long, [c_int] * 6),
-    "c2m_flow_warp_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_int, c_void_p]),
-    "c2m_resize_bilinear": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 5 + [c_double, c_int, c_void_p]),
-    "c2m_resize_bilinear_bwd": (c_int, [c_void_p, c_void_p, c_long] + [c_int] * 6 + [c_void_p]),
-    "c2m_upsample2x_fwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
-    "c2m_upsample2x_nc8": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p]),
-    "c2m_gat_dense_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p]),
-    "c2m_gat_dense_bwd_workspace_floats": (c_long, [c_int, c_int, c_int]),
-    "c2m_gat_dense_bwd": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_float, c_void_p]),
-    "c2m_upsample2x_bwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
-    "c2m_roi_align_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p]),
-    "c2m_roi_align_bwd": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_void_p]),
-    "c2m_maxpool2x2_fwd": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
-    "c2m_maxpool2x2_bwd": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_int, c_void_p]),
-    "c2m_maxpool2x2_relu_bwd": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_int, c_void_p]),
-    "c2m_sparse_raster": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p]),
-    "c2m_occlusion_splat_workspace_bytes": (c_long, [c_long, c_int, c_int]),
-    "c2m_occlusion_splat": (c_int, [c_void_p, c_long, c_long, c_long] + [c_int] * 4 + [c_void_p] * 4),
-    "c2m_label_warp": (c_int, [c_void_p, c_long, c_long, c_long, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 +
-                       [c_void_p] * 3),
-    "c2m_detail_warp": (c_int, [c_void_p] * 6 + [c_float, c_int] + [c_int] * 6 + [c_void_p] * 3),
-    "c2m_frame_quality_workspace_bytes": (c_long, [c_int] * 4),
-    "c2m_frame_quality": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3 + [c_double, c_void_p, c_long, c_void_p, c_void_p]),
-    "c2m_render_frames": (c_int, [c_void_p, c_int] + [c_int] * 8 + [c_void_p, c_void_p]),
-    "c2m_render_flow_workspace_bytes": (c_long, [c_int]),
-    "c2m_render_flow": (c_int, [c_void_p, c_int] + [c_int] * 7 + [c_float, c_void_p, c_void_p, c_void_p]),
-    "c2m_render_instances": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
-    "c2m_draw_overlays_max_boxes": (c_int, []),
-    "c2m_draw_overlays": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
-    "c2m_l1_mean_fwd": (c_int, [c_void_p] * 4 + [c_long, c_int, c_long, c_void_p, c_int, c_void_p]),
-    "c2m_relu_tap_bwd": (c_int, [c_void_p] * 5 + [c_long, c_int, c_void_p]),
-    "c2m_l1_mean_bwd": (c_int, [c_void_p] * 6 + [c_long, c_int, c_long, c_int, c_void_p]),
-    "c2m_ssim_fwd": (c_int, [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p, c_void_p]),
-    "c2m_ssim_bwd": (c_int, [c_void_p] * 5 + [c_long, c_int, c_int, c_void_p]),
-}
+
+def _parse_signatures(text):
+    """{name: (restype, [argtypes])} of every `int|long c2m_*(...)` prototype in the text of include/c2m_hip.h.  The compiler
+    holds the definitions in csrc/*.hip to the same prototypes (csrc/common.h includes the header), so this is the one place
+    a signature is written.  Anything the table below cannot express raises, naming the function: nothing defaults to int."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    sigs = {}
+    for ret, name, params in re.findall(r"\b(int|long)\s+(c2m_\w+)\s*\(([^()]*)\)\s*;", text):
+        if name in sigs:
+            raise ValueError(f"c2m_hip.h: {name} is declared twice")
+        args = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            tok = re.findall(r"\w+|\*", p)
+            if "".join(tok) != "".join(p.split()) or len(tok) < 2 or tok[-1] in _SCALARS or tok[-1] in ("*", "const", "void"):
+                raise ValueError(f"c2m_hip.h: {name}: cannot parse parameter {p.strip()!r} (want `type name`)")
+            ty = [t for t in tok[:-1] if t != "const"]
+            if "*" in ty[1:] and ty[0] != "*":
+                args.append(ctypes.c_void_p)
+            elif len(ty) == 1 and ty[0] in _SCALARS:
+                args.append(_SCALARS[ty[0]])
+            else:
+                raise ValueError(f"c2m_hip.h: {name}: parameter {p.strip()!r} has no ctypes mapping "
+                                 f"(by value: {', '.join(_SCALARS)}; or a pointer)")
+        sigs[name] = (_SCALARS[ret], args)
+    unparsed = sorted(set(re.findall(r"\b(c2m_\w+)\s*\(", text)) - set(sigs))
+    if unparsed:
+        raise ValueError(f"c2m_hip.h: cannot parse the prototype of {', '.join(unparsed)} (want `int|long name(type name, ...);`)")
+    return sigs
+
+
+with open(HEADER) as _f:
+    _SIGS = _parse_signatures(_f.read())
 
 
 GEOM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "c2m_geom.h")
@@ -165,9 +75,7 @@ ABI_VERSION, GEOM, WINO_GEOM = _parse_geom_header()
 
 def declared_symbols():
     """Every function name declared in include/c2m_hip.h."""
-    with open(HEADER) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\b(?:int|long)\s+(c2m_\w+)\s*\(", text)))
+    return sorted(_SIGS)
 
 
 def lib():

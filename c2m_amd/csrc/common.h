@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/c2m_geom.h"      // names of the geom[] entries (one definition for the library and the ctypes host)
+// The public header: every C2M_API definition is checked by the compiler against its prototype there, and the ctypes host parses
+// the same prototypes (c2m_amd/_lib.py).  It brings c2m_geom.h (names of the geom[] entries) and the C2M_ACT_* codes.
+#include "../../include/c2m_hip.h"
 
 #define C2M_API extern "C" __attribute__((visibility("default")))
 
@@ -77,8 +79,6 @@ __device__ __forceinline__ C2mBlock c2m_xcd_block(unsigned gx, unsigned gy, int 
     b.nz = gridDim.x / (gx * gy);
     return b;
 }
-
-enum { C2M_ACT_NONE = 0, C2M_ACT_RELU = 1, C2M_ACT_LRELU = 2, C2M_ACT_SIGMOID = 3 };
 
 __device__ __forceinline__ float c2m_act(float v, int act, float slope) {
     switch (act) {

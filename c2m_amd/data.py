@@ -14,16 +14,10 @@ from . import ops
 from .ops import _p, _stream
 
 
-def _dev(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("c2m_amd.data needs tensors on a HIP device (no CPU fallback by design)")
-
-
 def _u8(t, name):
     if t.dtype != torch.uint8:
         raise TypeError(f"{name} must be uint8 (decoded image data)")
-    _dev(t)
+    ops._hip_only(t)
     return t.contiguous()
 
 
@@ -52,14 +46,14 @@ def prep_flow_occ(occ_u8, flow_hwc):
     """occlusion PNGs [B,T,H,W] uint8 and .flo arrays [B,T,H,W,2] float32 -> (target_bw_occ [B,1,T,H,W],
     target_bw_of [B,2,T,H,W]) (cityscapes.py:212-231,254-265).  Either input may be None."""
     ref = occ_u8 if occ_u8 is not None else flow_hwc
-    _dev(ref)
+    ops._hip_only(ref)
     B, T, H, W = ref.shape[:4]
     occ = flow = None
     if occ_u8 is not None:
         occ_u8 = _u8(occ_u8, "occlusion")
         occ = torch.empty(B, 1, T, H, W, device=ref.device, dtype=torch.float32)
     if flow_hwc is not None:
-        _dev(flow_hwc)
+        ops._hip_only(flow_hwc)
         if flow_hwc.dtype != torch.float32 or tuple(flow_hwc.shape) != (B, T, H, W, 2):
             raise ValueError("flow must be float32 [B,T,H,W,2]")
         flow_hwc = flow_hwc.contiguous()
@@ -83,7 +77,7 @@ def _resize(x, name, dtypes, tail, size, run):
     """Shared front of the three resizes: x is [..., H, W] + tail dims; checks first, then one launch on the flattened batch."""
     if not torch.is_tensor(x) or x.dtype not in dtypes:
         raise TypeError(f"{name} must be a tensor of dtype {' or '.join(str(d) for d in dtypes)}")
-    _dev(x)
+    ops._hip_only(x)
     h, w = _size(size)
     cut = x.dim() - len(tail)                                  # [..., H, W] ends here
     if cut < 2 or any(c not in ok for c, ok in zip(x.shape[cut:], tail)):

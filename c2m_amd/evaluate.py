@@ -39,8 +39,7 @@ class Detector:
                 images.shape[2] % 32 or images.shape[2] < 32:
             raise ValueError(f"images must be [N,C,S,S] with S a multiple of 32, got "
                              f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__}")
-        if not images.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+        ops._hip_only(images)
         return self.net(images)
 
     def detect(self, images=None, conf_thres=0.5, nms_thres=0.4, heads=None, predictions=None, img_size=None):
@@ -76,8 +75,7 @@ def trajectory_metric(detector, video, generated, tracking_gnn, index_user_guida
     for name, t in (("video", video), ("generated", generated)):
         if not isinstance(t, torch.Tensor) or t.dim() != 5:
             raise ValueError(f"{name} must be [B,C,T,H,W]")
-        if not t.is_cuda:
-            raise RuntimeError(f"c2m_amd ops need tensors on a HIP device (no CPU fallback by design): {name}")
+        ops._hip_only(t, name=name, where=True)
     if video.shape[0] != generated.shape[0] or video.shape[1] != generated.shape[1] or video.shape[3:] != generated.shape[3:]:
         raise ValueError(f"video {tuple(video.shape)} and generated {tuple(generated.shape)} differ in batch, channels or size")
     B = video.shape[0]

@@ -44,14 +44,37 @@ def _dev(*ts):
         if t is None:
             continue
         if not t.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+            _hip_only(t)                # raises: the message is spelled there
         if t.dtype != torch.float32 and t.dtype != torch.bfloat16:
             raise RuntimeError(f"c2m_amd ops take fp32 (or, on the bf16 data path, bf16) tensors, got {t.dtype}")
         if cur is None:
             cur = _cur_device()
         if t.device.index != cur:       # kernels are launched on the CURRENT device's stream (see _stream)
-            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{cur}; "
-                               "call torch.cuda.set_device() (or use `with torch.cuda.device(...)`) first")
+            _on_current_device(t)       # raises
+
+
+def _hip_only(*ts, name=None, where=False, required=False):
+    """The device guard of every operator outside the training path (that one is _dev: it adds the dtype rule and reports through
+    these two): refuses a tensor that is not on a HIP device.  None and values that are no tensors pass (an operator's own checks
+    name those), unless `required`.  name: the argument, as a prefix of the message; with `where` appended instead, together with
+    the device it is on."""
+    for t in ts:
+        if t.is_cuda if isinstance(t, torch.Tensor) else not required:
+            continue
+        msg = "c2m_amd ops need tensors on a HIP device (no CPU fallback by design)"
+        if where:
+            raise RuntimeError(f"{msg}: {name} is on {t.device}")
+        raise RuntimeError(f"{name}: {msg}" if name else msg)
+
+
+def _on_current_device(*ts, name=None):
+    """Refuses a tensor (None passes) of another GPU than the current one: kernels are launched on the CURRENT device's stream
+    (see _stream), where such a tensor would arrive as a bare address."""
+    cur = _cur_device()
+    for t in ts:
+        if t is not None and t.device.index != cur:
+            raise RuntimeError(f"{name + ': ' if name else 'c2m_amd ops: '}tensor on cuda:{t.device.index} but the current device "
+                               f"is cuda:{cur}; call torch.cuda.set_device() (or use `with torch.cuda.device(...)`) first")
 
 
 def _f(t):
@@ -2479,8 +2502,7 @@ def sparse_raster(instance, obj_id, obj_batch, thetas):
 
 def _instance_input(instance, num_input_frames):
     """[B,1,T,H,W] or [B,T,H,W] integer ids on the device -> contiguous int32 [B,T,H,W] (no copy for an int32 input)."""
-    if not instance.is_cuda:
-        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(instance)
     if instance.dim() == 5:
         if instance.shape[1] != 1:
             raise ValueError(f"instance maps must be [B,1,T,H,W] or [B,T,H,W], got {tuple(instance.shape)}")
@@ -2491,9 +2513,7 @@ def _instance_input(instance, num_input_frames):
         raise TypeError(f"instance maps hold integer ids, got {instance.dtype}")
     if not 1 <= num_input_frames <= instance.shape[1]:
         raise ValueError(f"num_input_frames={num_input_frames} but the maps have {instance.shape[1]} frames")
-    if instance.device.index != _cur_device():
-        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{instance.device.index} but the current device is "
-                           f"cuda:{_cur_device()}")
+    _on_current_device(instance)
     return _f(instance if instance.dtype == torch.int32 else instance.to(torch.int32))
 
 
@@ -2557,14 +2577,12 @@ def _link_nodes(max_nodes, min_pixels=1):
 
 def _link_i32(name, t, shape):
     """An int32 device tensor of exactly `shape` on the current device, contiguous."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(t, required=True)
     if t.dtype != torch.int32:
         raise TypeError(f"{name} must be int32, got {t.dtype}")
     if tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-    if t.device.index != _cur_device():
-        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    _on_current_device(t)
     return _f(t)
 
 
@@ -2579,8 +2597,7 @@ def instance_slots(table, id_range=(1000, 19000), min_pixels=1, max_nodes=64):
     id_lo, id_hi = (int(v) for v in id_range)
     if not 0 <= id_lo < id_hi:
         raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
-    if not isinstance(table, torch.Tensor) or not table.is_cuda:
-        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(table, required=True)
     if table.dim() < 2 or tuple(table.shape[-2:]) != (id_hi - id_lo, 5):
         raise ValueError(f"table must be [..., {id_hi - id_lo}, 5] for id_range {id_range}, got {list(table.shape)}")
     lead = tuple(table.shape[:-2])
@@ -2621,14 +2638,12 @@ def instance_overlap(ref, frame, flow, ref_slots, ref_count, frame_slots, frame_
     if H * W >= 2 ** 31:
         raise ValueError(f"a plane of {H}x{W} pixels is too large (H * W must be below 2**31)")
     if flow is not None:
-        if not flow.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+        _hip_only(flow)
         if flow.dtype != torch.float32:
             raise TypeError(f"flow must be fp32 (coordinates are never rounded), got {flow.dtype}")
         if tuple(flow.shape) != (P, 2, H, W):
             raise ValueError(f"flow must be {[P, 2, H, W]} (at the size of the maps), got {list(flow.shape)}")
-        if flow.device.index != _cur_device():
-            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{flow.device.index} but the current device is cuda:{_cur_device()}")
+        _on_current_device(flow)
         flow = _f(flow.detach())
     pairs = torch.empty(P, M + 1, M + 1, device=ref.device, dtype=torch.int32)
     if P:
@@ -2727,15 +2742,11 @@ def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fil
     planes_i [B,Ci,H,W] int32, either may be None or have 0 channels.  occ [B,1,T,H,W] (or [B,1,H,W]) with `threshold`: where
     occ < threshold the INTEGER outputs are `fill_id`; float planes are not touched.
     Returns (out_f [B,Cf,T,H,W] fp32 or None, out_i [B,Ci,T,H,W] int32 or None).  One launch, no atomics, no autograd."""
-    for t in (flow, planes_f, planes_i, occ):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(flow, planes_f, planes_i, occ)
     B, T, H, W, Cf, Ci = _label_warp_plan(flow, planes_f, planes_i, occ, threshold)
     if not -2 ** 31 <= int(fill_id) < 2 ** 31:
         raise ValueError(f"fill_id must be an int32 value, got {fill_id}")
-    for t in (flow, planes_f, planes_i, occ):
-        if t is not None and t.device.index != _cur_device():
-            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    _on_current_device(flow, planes_f, planes_i, occ)
     flow = flow.detach()
     if flow.stride(-1) != 1 or flow.stride(-2) != W:
         flow = flow.contiguous()
@@ -2806,15 +2817,11 @@ def detail_warp(frame_u8, generated, warped, flow, occ=None, ids=None, occ_thres
     blended; with occ_threshold, fill_id where up(occ) < occ_threshold.
     Returns (uint8 [B,T,H,W,3], int32 [B,T,H,W] or None).  One launch, no atomics, no autograd."""
     ts = (frame_u8, generated, warped, flow, occ, ids)
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(*ts)
     B, T, h, w, H, W = _detail_warp_plan(frame_u8, generated, warped, flow, occ, ids, occ_threshold)
     if not -2 ** 31 <= int(fill_id) < 2 ** 31:
         raise ValueError(f"fill_id must be an int32 value, got {fill_id}")
-    for t in ts:
-        if t is not None and t.device.index != _cur_device():
-            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    _on_current_device(*ts)
     frame_u8, ids = _f(frame_u8), None if ids is None else _f(ids)
     generated, warped = _as(generated.detach(), torch.float32), _as(warped.detach(), torch.float32)
     flow, occ = _f(flow.detach()), None if occ is None else _as(occ.detach(), torch.float32)
@@ -2895,13 +2902,9 @@ def frame_quality(pred, target, regions=None):
     copy.  regions: uint8 [B,T,H,W] or None.  sse counts every pixel; ssim_sum the centres whose 11x11 Gaussian window (sigma
     1.5) lies inside the frame, SSIM as skimage's structural_similarity(gaussian_weights=True, use_sample_covariance=False)
     computes it, in fp64.  Two launches, no atomics, bit-repeatable, no autograd."""
-    for t in (pred, target, regions):
-        if isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(pred, target, regions)
     form, B, C, T, H, W = _frame_quality_plan(pred, target, regions)
-    for t in (pred, target, regions):
-        if t is not None and t.device.index != _cur_device():
-            raise RuntimeError(f"c2m_amd ops: tensor on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    _on_current_device(pred, target, regions)
     pred, target = pred.detach(), target.detach()
     if pred.dtype != target.dtype:                       # fp32 against bf16: bf16 -> fp32 is exact
         pred, target = pred.float(), target.float()
@@ -2933,10 +2936,8 @@ def _sheet_plan(name, x, channels, size, dtypes=(torch.float32, torch.bfloat16))
     rows, cols = (int(v) for v in size)
     if rows < 1 or cols < 1 or x.shape[0] > rows * cols:
         raise ValueError(f"{name}: B = {x.shape[0]} samples do not fit size = {rows} x {cols} cells")
-    if not x.is_cuda:                   # after the shape checks: those are the same with or without a device
-        raise RuntimeError(f"{name}: c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
-    if x.device.index != _cur_device():
-        raise RuntimeError(f"{name}: tensor on cuda:{x.device.index} but the current device is cuda:{_cur_device()}")
+    _hip_only(x, name=name)             # after the shape checks: those are the same with or without a device
+    _on_current_device(x, name=name)
     B, C, T, H, W = x.shape
     return B, C, T, H, W, rows, cols
 
@@ -3017,10 +3018,8 @@ def draw_overlays(sheet, size, boxes=None, presence=None, box_colors=None, point
     belongs to), point_count [D,T] (frame t shows the first point_count[d, t] points and a 3x3 marker on the last of them),
     line_colors [D,3] uint8.  Per pixel the last covering primitive wins: boxes in node order, then paths in order; nothing is
     drawn outside a sample's own cell."""
-    if not isinstance(sheet, torch.Tensor) or not sheet.is_cuda:
-        raise RuntimeError("sheet: c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
-    if sheet.device.index != _cur_device():
-        raise RuntimeError(f"sheet: tensor on cuda:{sheet.device.index} but the current device is cuda:{_cur_device()}")
+    _hip_only(sheet, name="sheet", required=True)
+    _on_current_device(sheet, name="sheet")
     if sheet.dtype != torch.uint8 or sheet.dim() != 4 or sheet.shape[-1] != 3 or not sheet.is_contiguous():
         raise ValueError(f"sheet must be a contiguous uint8 [T, rows*H, cols*W, 3] tensor, got {sheet.dtype} {tuple(sheet.shape)}")
     rows, cols = (int(v) for v in size)
@@ -3293,10 +3292,8 @@ _DET_MAX_HEADS, _DET_MAX_ANCHORS = 4, 8
 def _det_check(name, t, dtype, dim=None):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-    if not t.is_cuda:
-        raise RuntimeError(f"c2m_amd ops need tensors on a HIP device (no CPU fallback by design): {name} is on {t.device}")
-    if t.device.index != _cur_device():
-        raise RuntimeError(f"c2m_amd ops: {name} on cuda:{t.device.index} but the current device is cuda:{_cur_device()}")
+    _hip_only(t, name=name, where=True)
+    _on_current_device(t, name=name)
     if t.dtype != dtype:
         raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
     if dim is not None and t.dim() != dim:
@@ -3527,12 +3524,9 @@ def panoptic_maps(semantic, center, offset, thing_list, label_divisor, stuff_are
     offset [N,2,H,W] (dy, dx) fp32.  Returns device tensors: semantic uint8, instance int32, panoptic int32 [N,H,W], centers
     int32 [N,top_k,2] (y, x; zero past the count) and center_count int32 [N].  Six launches on the current stream; nothing is read
     back and nothing synchronises."""
-    for t in (semantic, center, offset):
-        if isinstance(t, torch.Tensor) and not t.is_cuda:
-            raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    _hip_only(semantic, center, offset)
     pl = _panoptic_plan(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k)
-    if semantic.device.index != _cur_device():
-        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{semantic.device.index} but the current device is cuda:{_cur_device()}")
+    _on_current_device(semantic, center, offset)
     L = _lib.lib()
     assert L.c2m_panoptic_max_top_k() == PANOPTIC_MAX_TOP_K
     dev = semantic.device
@@ -3613,10 +3607,8 @@ def map_quality(pred, gt, num_classes, thing_list, label_divisor, ignore_label, 
     Returns device tensors: tp, fp, fn int32 [N,C], iou float64 [N,C], confusion int64 [N,C+1,C+1] ([pred, gt], void last),
     overflow bool [N].  A zero-fill and three launches on the current stream; nothing is read back and nothing synchronises."""
     pl = _map_quality_plan(pred, gt, num_classes, thing_list, label_divisor, ignore_label, max_pairs)
-    if not (pred.is_cuda and gt.is_cuda):
-        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
-    if pred.device.index != _cur_device():
-        raise RuntimeError(f"c2m_amd ops: tensor on cuda:{pred.device.index} but the current device is cuda:{_cur_device()}")
+    _hip_only(pred, gt)
+    _on_current_device(pred, gt)
     L = _lib.lib()
     dev, N, C = pred.device, pl.N, pl.num_classes
     pred, gt = pred.detach(), gt.detach()

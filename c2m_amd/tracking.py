@@ -96,8 +96,7 @@ def _flow_input(name, flow, B, frames, H, W):
                          "sizes (common_params.scale_factor != 1) are not supported yet")
     if flow.shape[0] != B or flow.shape[2] != frames:
         raise ValueError(f"{name} must be {[B, 2, frames, H, W]} for these maps, got {list(flow.shape)}")
-    if not flow.is_cuda:
-        raise RuntimeError("c2m_amd ops need tensors on a HIP device (no CPU fallback by design)")
+    ops._hip_only(flow)
     return flow.detach()
 
 

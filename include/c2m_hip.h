@@ -5,6 +5,11 @@
  * /root/reference/src) whose ATen op chain it replaces; the Python-side binding is the ctypes stub in
  * c2m_amd/_lib.py (shown in INTEGRATION.md).
  *
+ * This header is the ONE definition of every signature.  csrc/common.h includes it, so the compiler holds each definition in
+ * the .hip files under csrc/ to its prototype, and c2m_amd/_lib.py parses the prototypes below into its ctypes table at import.  Keep them in the
+ * form the parser reads -- `int|long c2m_name(type name, ...);`, by-value types int, unsigned, long, float, double (or int32_t,
+ * int64_t, uint8_t), anything with a `*` is passed as a pointer -- or the import raises, naming the function.
+ *
  * Conventions (every function):
  *   - plain pointers to DEVICE memory, fp32 unless noted, contiguous NCHW / NCTHW; sizes as int / long
  *   - `stream` is a hipStream_t passed as void*; kernels are enqueued on it and never synchronise or allocate;

@@ -247,3 +247,79 @@ def test_geom_names_one_definition_for_kernels_and_host():
     assert len(g) == G.LEN and int(g[G.NCLS]) == 8 and int(g[G.X_TYPE]) == 0 and int(g[G.Y_TYPE]) == 0 and int(g[G.WGRAD_WIDE]) == 0
     assert [tuple(int(v) for v in g[G.CLS_PO + 3 * c:G.CLS_PO + 3 * c + 3]) for c in range(8)] == \
         [(a, b, c) for a in range(2) for b in range(2) for c in range(2)]
+
+
+# --------------------------------------------------------------- include/c2m_hip.h: the one definition of every signature
+def test_ctypes_signatures_are_parsed_from_the_header():
+    """_lib._SIGS is derived from include/c2m_hip.h; the rows below are copied from the hand-written table it replaced (one per
+    branch of the parser)."""
+    V, I, L, F, D, U = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double, ctypes.c_uint
+    want = {
+        "c2m_abi_version": (I, []),                                                               # (void)
+        "c2m_pack_job_fill": (L, [V, I, V, V, V, U]),                                             # long return, unsigned
+        "c2m_yolo_candidates": (I, [V] * 5 + [I] * 4 + [F, I] + [V] * 5),                         # const void* const*
+        "c2m_splitk_reduce": (I, [V] * 3 + [L, I, L, I, I, F, I, V]),                             # a comment between parameters
+        "c2m_frame_quality": (I, [V] * 3 + [I] * 6 + [V] * 3 + [D, V, L, V, V]),                  # const long*, double, long
+        "c2m_match_detections": (I, [V, V, I, I, V, I, V, I, V, I, I, V, L, I, I, I, D, D] + [V] * 4),
+        "c2m_label_warp": (I, [V, L, L, L, V, F, I, V, I, V, I] + [I] * 4 + [V] * 3),             # int32_t*, long strides
+        "c2m_occlusion_splat_workspace_bytes": (L, [L, I, I]),                                    # long return, long first
+    }
+    for name, (res, args) in want.items():
+        got = _lib._SIGS[name]
+        assert got[0] is res and list(got[1]) == args, f"{name}: {got}"
+    assert len(_lib._SIGS) == len(_lib.declared_symbols()) >= 119
+    assert _lib.declared_symbols() == sorted(_lib._SIGS)
+
+
+def test_header_parser_refuses_what_it_does_not_know():
+    parse = _lib._parse_signatures
+    with pytest.raises(ValueError, match="c2m_takes_size"):                    # a by-value type outside the table
+        parse("int c2m_fine(int a);\nint c2m_takes_size(const float* x, size_t n, void* stream);")
+    with pytest.raises(ValueError, match="c2m_twice.*twice"):
+        parse("int c2m_twice(int a);\nlong c2m_other(void);\nint c2m_twice(int a);")
+    with pytest.raises(ValueError, match="c2m_opaque"):                        # a struct by value
+        parse("int c2m_opaque(struct c2m_job job, void* stream);")
+    with pytest.raises(ValueError, match="c2m_unnamed"):                       # `type name`, both
+        parse("int c2m_unnamed(const float*, int n);")
+    with pytest.raises(ValueError, match="c2m_returns_size"):                  # a prototype the pattern does not cover
+        parse("size_t c2m_returns_size(int n);")
+    got = parse("/* int c2m_in_a_comment(int a); */\n"
+                "long c2m_spread(const float* x,   // the input\n"
+                "                int32_t* const* tables, unsigned n,\n"
+                "                double eps, void* stream);   /* trailing\n comment */\n"
+                "int c2m_none();\n")
+    assert got == {"c2m_spread": (ctypes.c_long, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_double,
+                                                  ctypes.c_void_p]),
+                   "c2m_none": (ctypes.c_int, [])}
+
+
+def test_definition_that_disagrees_with_the_header_does_not_compile(tmp_path):
+    """csrc/common.h includes include/c2m_hip.h, so a C2M_API definition whose types differ from its prototype is a compile error.
+    Syntax check only: nothing is linked or run."""
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("hipcc not found")
+    common = os.path.join(c2m_build.CSRC, "common.h")
+    results = {}
+    for tag, second in (("agrees", "int"), ("widened", "long")):
+        src = tmp_path / f"{tag}.hip"
+        src.write_text(f'#include "{common}"\nC2M_API int c2m_wino_regions(int Ho, {second} Wo) {{ return Ho + (int)Wo; }}\n')
+        results[tag] = subprocess.run([hipcc, f"--offload-arch={c2m_build.ARCH}", "-fsyntax-only", "-fvisibility=hidden", str(src)],
+                                      capture_output=True, text=True)
+    assert results["agrees"].returncode == 0, results["agrees"].stderr       # the control: the include path works
+    assert results["widened"].returncode != 0 and "conflicting types" in results["widened"].stderr, results["widened"].stderr
+
+
+def test_build_tracks_the_public_header(monkeypatch):
+    """An edit of include/c2m_hip.h rebuilds every object: the header is among the dependencies of each (nothing is built here)."""
+    seen = []
+    monkeypatch.setattr(c2m_build, "_stale", lambda target, deps: seen.append((target, list(deps))) or False)
+    monkeypatch.setattr(c2m_build.subprocess, "check_call", lambda *a, **k: pytest.fail("the test must not build"))
+    c2m_build.build()
+    objects = [(t, deps) for t, deps in seen if t.endswith(".o")]
+    assert len(objects) == len(c2m_build.SOURCES)
+    for target, deps in objects:
+        assert os.path.samefile(_lib.HEADER, next(d for d in deps if d.endswith("c2m_hip.h"))), target
+        assert any(d.endswith("c2m_geom.h") for d in deps) and any(d.endswith("common.h") for d in deps)

@@ -182,3 +182,37 @@ def test_host_checks_come_before_any_launch():
         evaluate.map_quality(a[:, None], a[:, :1])
     with pytest.raises(RuntimeError, match="no CPU fallback"):    # every check passed: a host tensor is refused, never scored
         evaluate.map_quality(a, a)
+
+
+def test_both_maps_are_guarded_on_the_launch_path(monkeypatch):
+    """The device guards look at every operand (a host tensor or another GPU's in any position), and map_quality hands them gt as
+    well as pred."""
+    from c2m_amd import ops
+    monkeypatch.setattr(ops, "_cur_device", lambda: 0)
+    on = lambda index: type("OnGpu", (), {"is_cuda": True, "device": type("device", (), {"index": index})()})()
+    ops._on_current_device(on(0), on(0), None)
+    for operands in ((on(1), on(0)), (on(0), on(1)), (None, on(0), on(1))):
+        with pytest.raises(RuntimeError, match="tensor on cuda:1 but the current device is cuda:0"):
+            ops._on_current_device(*operands)
+    host = torch.zeros(1, 4, 6, dtype=torch.int32)
+    ops._hip_only(None, None)
+    for operands in ((host, None), (None, host)):
+        with pytest.raises(RuntimeError, match="HIP device .no CPU fallback by design.$"):
+            ops._hip_only(*operands)
+
+    class Reached(Exception):
+        pass
+
+    seen = {}
+
+    def on_current_device(*ts, **kw):
+        seen["current"] = ts
+        raise Reached
+
+    monkeypatch.setattr(ops, "_hip_only", lambda *ts, **kw: seen.__setitem__("hip", ts))
+    monkeypatch.setattr(ops, "_on_current_device", on_current_device)
+    pred, gt = host, host.clone()
+    with pytest.raises(Reached):
+        ops.map_quality(pred, gt, 19, tuple(range(11, 19)), 1000, 255, 1 << 12)
+    for guard in ("hip", "current"):
+        assert any(t is pred for t in seen[guard]) and any(t is gt for t in seen[guard]), guard

@@ -159,3 +159,47 @@ def test_entry_points_are_declared_and_bound():
     for name in ("c2m_panoptic_maps", "c2m_panoptic_workspace_bytes", "c2m_panoptic_max_top_k"):
         assert name in _lib.declared_symbols() and name in _lib._SIGS
     assert _lib.ABI_VERSION == 6                                          # additive: no geom[] entry moved
+
+
+class _OnGpu:
+    """Stands for a tensor on GPU `index`: what the current-device guard reads of one."""
+    is_cuda = True
+
+    def __init__(self, index):
+        self.device = type("device", (), {"index": index})()
+
+
+def test_every_head_is_guarded_on_the_launch_path(monkeypatch):
+    """The two device guards (ops._hip_only, ops._on_current_device) look at every operand, and panoptic_maps hands them all three
+    heads: center and offset on another GPU would otherwise reach the kernel as bare addresses."""
+    monkeypatch.setattr(ops, "_cur_device", lambda: 0)
+    here, there, host = _OnGpu(0), _OnGpu(1), torch.zeros(1)
+    ops._on_current_device(here, None, here)
+    for operands in ((there, here, here), (here, there, None), (here, None, there)):
+        with pytest.raises(RuntimeError, match="tensor on cuda:1 but the current device is cuda:0"):
+            ops._on_current_device(*operands)
+    ops._hip_only(None, "no tensor", None)
+    for operands in ((host, None, None), (None, host), (None, "no tensor", host)):
+        with pytest.raises(RuntimeError, match=r"^c2m_amd ops need tensors on a HIP device \(no CPU fallback by design\)$"):
+            ops._hip_only(*operands)
+    with pytest.raises(RuntimeError, match=r"^offset: c2m_amd ops need tensors on a HIP device \(no CPU fallback by design\)$"):
+        ops._hip_only(None, host, name="offset")
+    with pytest.raises(RuntimeError, match="HIP device"):
+        ops._hip_only(None, required=True)
+
+    class Reached(Exception):
+        pass
+
+    seen = {}
+
+    def on_current_device(*ts, **kw):
+        seen["current"] = ts
+        raise Reached
+
+    monkeypatch.setattr(ops, "_hip_only", lambda *ts, **kw: seen.__setitem__("hip", ts))
+    monkeypatch.setattr(ops, "_on_current_device", on_current_device)
+    heads = _heads()
+    with pytest.raises(Reached):
+        segment.panoptic_maps(*heads)
+    for guard in ("hip", "current"):
+        assert all(any(t is h for t in seen[guard]) for h in heads), guard
