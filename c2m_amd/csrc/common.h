@@ -5,6 +5,8 @@
 // The public header: every C2M_API definition is checked by the compiler against its prototype there, and the ctypes host parses
 // the same prototypes (c2m_amd/_lib.py).  It brings c2m_geom.h (names of the geom[] entries) and the C2M_ACT_* codes.
 #include "../../include/c2m_hip.h"
+// wave_sum / block_sum_256, wave_rank / block_rank_256, wave_key_step / wave_merge_add, c2m_aligned
+#include "wave.h"
 
 #define C2M_API extern "C" __attribute__((visibility("default")))
 
@@ -28,37 +30,6 @@ static inline int c2m_grid(long work_items, int block) {
     if (g > cap) g = cap;
     if (g < 1) g = 1;
     return (int)g;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// Block-wide sum for blockDim.x == 256 (4 waves). Result valid in every thread.
-__device__ __forceinline__ float block_sum_256(float v, float* smem /* >= 4 floats */) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) smem[wave] = v;
-    __syncthreads();
-    return smem[0] + smem[1] + smem[2] + smem[3];
-}
-
-__device__ __forceinline__ double block_sum_256_d(double v, double* smem /* >= 4 doubles */) {
-    v = wave_sum_d(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) smem[wave] = v;
-    __syncthreads();
-    return smem[0] + smem[1] + smem[2] + smem[3];
 }
 
 // XCD-aware work order.  Workgroups of a launch are handed to the 8 XCDs round-robin by linear id and every XCD has its own

@@ -8,6 +8,7 @@
 // never builds the 20-channel one-hot volumes (20x the bytes of the label map).
 // (v/255)*255 == v holds exactly in fp32 for every uint8 v, so the one-hot test is an integer compare.
 #include "common.h"
+#include "instance_compact.h"
 
 // frames [B][T][H][W][3] uint8 -> video [B][3][T][H][W] float, x / 255 (true division, as Tensor.div(255))
 __global__ void prep_video_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, long BT, int T, long HW) {
@@ -184,63 +185,15 @@ C2M_API int c2m_instance_stats(const int32_t* instance, int32_t* table, int B, i
     return (int)hipGetLastError();
 }
 
-// One workgroup (256 threads) per sample: the ids present in EVERY input frame with count >= min_pixels, in ascending id
-// order.  Slots come from an ordered block-wide prefix scan (ballot + popcount per wave, wave totals through LDS), so the
-// output does not depend on scheduling.  ids [B][max_nodes], boxes [B][max_nodes][t_in][4] = (x_min, y_min, x_max+1,
-// y_max+1), count [B] (kept objects, <= max_nodes), overflow [B] (1: more than max_nodes objects; the rest is dropped).
-// Slots past count are zero.
-__global__ void instance_compact_kernel(const int* __restrict__ table, int* __restrict__ ids, int* __restrict__ boxes,
-                                        int* __restrict__ count, int* __restrict__ overflow, int t_in, int nid, int id_lo,
-                                        int min_pixels, int max_nodes) {
-    __shared__ int wave_tot[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int* __restrict__ tab = table + (long)b * t_in * nid * 5;
-    int* __restrict__ my_ids = ids + (long)b * max_nodes;
-    int* __restrict__ my_boxes = boxes + (long)b * max_nodes * t_in * 4;
-    int base = 0;
-    for (int j0 = 0; j0 < nid; j0 += 256) {
-        const int j = j0 + tid;
-        bool keep = j < nid;
-        for (int t = 0; t < t_in && keep; ++t) keep = tab[((long)t * nid + j) * 5] >= min_pixels;
-        const unsigned long long m = __ballot(keep);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_tot[wv] = __popcll(m);
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wv; ++w) off += wave_tot[w];
-        const int total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-        const int slot = base + off + before;
-        if (keep && slot < max_nodes) {
-            my_ids[slot] = id_lo + j;
-            for (int t = 0; t < t_in; ++t) {
-                const int* __restrict__ e = tab + ((long)t * nid + j) * 5;
-                int* __restrict__ o = my_boxes + ((long)slot * t_in + t) * 4;
-                o[0] = e[1];
-                o[1] = e[3];
-                o[2] = e[2] + 1;
-                o[3] = e[4] + 1;
-            }
-        }
-        base += total;
-        __syncthreads();                                                  // wave_tot is rewritten by the next chunk
-    }
-    const int kept = min(base, max_nodes);
-    for (int s = kept + tid; s < max_nodes; s += 256) {
-        my_ids[s] = 0;
-        for (int k = 0; k < t_in * 4; ++k) my_boxes[(long)s * t_in * 4 + k] = 0;
-    }
-    if (tid == 0) {
-        count[b] = kept;
-        overflow[b] = base > max_nodes ? 1 : 0;
-    }
-}
-
+// The objects of a sample: the ids present in EVERY input frame with count >= min_pixels, in ascending id order
+// (instance_compact.h; one workgroup per sample).  ids [B][max_nodes], boxes [B][max_nodes][t_in][4], count [B], overflow [B].
+// Slots past count are zero.  No cap on max_nodes.
 C2M_API int c2m_instance_compact(const int32_t* table, int32_t* ids, int32_t* boxes, int32_t* count, int32_t* overflow,
                                  int B, int t_in, int nid, int id_lo, int min_pixels, int max_nodes, void* stream) {
     C2M_ENTER();
     if (B < 0 || t_in < 1 || nid < 1 || min_pixels < 1 || max_nodes < 1) return (int)hipErrorInvalidValue;
     if (B == 0) return 0;
-    hipLaunchKernelGGL(instance_compact_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, table, ids, boxes, count,
-                       overflow, t_in, nid, id_lo, min_pixels, max_nodes);
+    hipLaunchKernelGGL(instance_compact_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, table, ids, boxes,
+                       (int*)nullptr, count, overflow, t_in, nid, id_lo, min_pixels, max_nodes, 0);
     return (int)hipGetLastError();
 }

@@ -165,7 +165,7 @@ C2M_API int c2m_detail_warp(const uint8_t* frame, const float* generated, const 
     DetailWarpP p{frame, generated, warped, flow, occ, ids, out, out_ids, threshold, (int32_t)fill_id,
                   (float)w / (float)W, (float)h / (float)H, B, T, h, w, H, W,
                   dw_patch(DW_TILE_H, h, H), dw_patch(DW_TILE_W, w, W), (unsigned)tiles_x, (unsigned)tiles_y, 0};
-    p.vec = W % DW_RUN == 0 && (((uintptr_t)out) & 3) == 0 && (!ids || (((uintptr_t)out_ids) & 15) == 0);
+    p.vec = W % DW_RUN == 0 && c2m_aligned(4, out) && (!ids || c2m_aligned(16, out_ids));
     const size_t lds = (size_t)DW_PLANES * p.ph * p.pw * sizeof(float);           // <= 9 * 6 * 258 * 4 = 55728 bytes
     hipLaunchKernelGGL(detail_warp_kernel, dim3((unsigned)tiles), dim3(256), lds, (hipStream_t)stream, p);
     return (int)hipGetLastError();

@@ -93,15 +93,9 @@ __global__ __launch_bounds__(C2M_DET_BLOCK) void yolo_count_kernel(DetHeads hd, 
         const DetBox b = det_locate(hd, C, n, j);
         pass = det_sigmoid(b.base[4 * b.plane]) >= conf_thres;
     }
-    const int c = __popcll(__ballot(pass));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < C2M_DET_BLOCK / 64; ++w) s += wsum[w];
-        block_count[blockIdx.x] = s;
-    }
+    int passing;
+    (void)block_rank_256(pass, wsum, passing);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = passing;
 }
 
 // pass 2: each block sums the counts of the blocks before it (at most 41 at 416 x 416), decodes its passing boxes and writes
@@ -123,11 +117,8 @@ __global__ __launch_bounds__(C2M_DET_BLOCK) void yolo_scatter_kernel(DetHeads hd
             t += v;
             if (k < blk) s += v;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_down(s, o, 64);
-            t += __shfl_down(t, o, 64);
-        }
+        s = wave_sum(s);
+        t = wave_sum(t);
         if (lane == 0) {
             base_s = s;
             if (blk == 0) count[n] = t;
@@ -142,12 +133,10 @@ __global__ __launch_bounds__(C2M_DET_BLOCK) void yolo_scatter_kernel(DetHeads hd
         conf = det_sigmoid(b.base[4 * b.plane]);
         pass = conf >= conf_thres;
     }
-    const unsigned long long m = __ballot(pass);
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
+    int passing;
+    int rank = block_rank_256(pass, wsum, passing);      // its barrier publishes base_s as well
     if (!pass) return;
-    int rank = base_s + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += wsum[w];
+    rank += base_s;
     if (rank >= cap) return;                 // cannot happen (cap >= boxes per image is checked on the host)
     const float st = hd.stride[b.h];
     const float cx = (det_sigmoid(b.base[0]) + (float)b.gx) * st;

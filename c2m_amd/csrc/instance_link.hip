@@ -3,8 +3,8 @@
 // (cityscapes.py:79-199); c2m_amd.tracking builds the same [T, N] id table from maps and flows with these three entries.
 //
 //   c2m_instance_slots    per plane of the c2m_instance_stats table, the ids with count >= min_pixels in ascending order
-//                         (the ballot + popcount compaction of instance_compact_kernel without its "in every input frame" rule),
-//                         their boxes and areas.  An id's position in that list is its SLOT.
+//                         (the one-plane form of instance_compact_kernel, instance_compact.h: its "in every input frame" rule
+//                         is void), their boxes and areas.  An id's position in that list is its SLOT.
 //   c2m_instance_overlap  contingency table of two maps: pairs[p][i][j] = number of frame pixels q whose id has frame slot j and
 //                         whose SOURCE pixel in the reference map holds an id with reference slot i.  The source pixel is the
 //                         one c2m_label_warp reads for q (warp_coord.h: warp_source, border clamp, rintf), or q itself without
@@ -14,6 +14,7 @@
 // All arithmetic after the source coordinate is integer and the only atomics are int32 adds, so every output is bit-repeatable.
 // This file is compiled with -ffp-contract=off (see warp_coord.h).
 #include "common.h"
+#include "instance_compact.h"
 #include "warp_coord.h"
 
 #define C2M_LINK_MAX_NODES 64                  // one wave holds a plane's slots: one lane per slot
@@ -23,57 +24,10 @@
 C2M_API int c2m_instance_link_max_nodes(void) { return C2M_LINK_MAX_NODES; }
 
 // ------------------------------------------------------------------------------------------------ slots
-// One workgroup (256 threads) per plane.  table [planes][nid][5] (count, x_min, x_max, y_min, y_max); slot_ids [planes][max_nodes]
-// (-1 past count: ids are >= id_lo >= 0, so a padding slot matches no pixel), boxes [planes][max_nodes][4] = (x_min, y_min,
-// x_max + 1, y_max + 1), areas [planes][max_nodes] (both zero past count), count [planes], overflow [planes].
-__global__ __launch_bounds__(256) void instance_slots_kernel(const int* __restrict__ table, int* __restrict__ slot_ids,
-                                                             int* __restrict__ boxes, int* __restrict__ areas,
-                                                             int* __restrict__ count, int* __restrict__ overflow, int nid,
-                                                             int id_lo, int min_pixels, int max_nodes) {
-    __shared__ int wave_tot[4];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int* __restrict__ tab = table + (long)p * nid * 5;
-    int* __restrict__ my_ids = slot_ids + (long)p * max_nodes;
-    int* __restrict__ my_boxes = boxes + (long)p * max_nodes * 4;
-    int* __restrict__ my_areas = areas + (long)p * max_nodes;
-    int base = 0;
-    for (int j0 = 0; j0 < nid; j0 += 256) {
-        const int j = j0 + tid;
-        const int cnt = j < nid ? tab[(long)j * 5] : 0;
-        const bool keep = j < nid && cnt >= min_pixels;
-        const unsigned long long m = __ballot(keep);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_tot[wv] = __popcll(m);
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wv; ++w) off += wave_tot[w];
-        const int total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-        const int slot = base + off + before;
-        if (keep && slot < max_nodes) {
-            const int* __restrict__ e = tab + (long)j * 5;
-            my_ids[slot] = id_lo + j;
-            my_areas[slot] = cnt;
-            int* __restrict__ o = my_boxes + (long)slot * 4;
-            o[0] = e[1];
-            o[1] = e[3];
-            o[2] = e[2] + 1;
-            o[3] = e[4] + 1;
-        }
-        base += total;
-        __syncthreads();                                                  // wave_tot is rewritten by the next chunk
-    }
-    const int kept = min(base, max_nodes);
-    for (int s = kept + tid; s < max_nodes; s += 256) {
-        my_ids[s] = -1;
-        my_areas[s] = 0;
-        for (int k = 0; k < 4; ++k) my_boxes[(long)s * 4 + k] = 0;
-    }
-    if (tid == 0) {
-        count[p] = kept;
-        overflow[p] = base > max_nodes ? 1 : 0;
-    }
-}
-
+// The one-plane form of the compaction of instance_compact.h: one workgroup per plane, with areas.  table [planes][nid][5]
+// (count, x_min, x_max, y_min, y_max); slot_ids [planes][max_nodes] (-1 past count: ids are >= id_lo >= 0, so a padding slot
+// matches no pixel), boxes [planes][max_nodes][4] = (x_min, y_min, x_max + 1, y_max + 1), areas [planes][max_nodes] (both zero
+// past count), count [planes], overflow [planes].
 C2M_API int c2m_instance_slots(const int32_t* table, int32_t* slot_ids, int32_t* boxes, int32_t* areas, int32_t* count,
                                int32_t* overflow, int planes, int nid, int id_lo, int min_pixels, int max_nodes,
                                void* stream) {
@@ -82,8 +36,8 @@ C2M_API int c2m_instance_slots(const int32_t* table, int32_t* slot_ids, int32_t*
         return (int)hipErrorInvalidValue;
     if (planes == 0) return 0;
     if (!table || !slot_ids || !boxes || !areas || !count || !overflow) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(instance_slots_kernel, dim3(planes), dim3(256), 0, (hipStream_t)stream, table, slot_ids, boxes, areas,
-                       count, overflow, nid, id_lo, min_pixels, max_nodes);
+    hipLaunchKernelGGL(instance_compact_kernel<true>, dim3(planes), dim3(256), 0, (hipStream_t)stream, table, slot_ids, boxes,
+                       areas, count, overflow, 1, nid, id_lo, min_pixels, max_nodes, -1);
     return (int)hipGetLastError();
 }
 
@@ -94,19 +48,6 @@ __device__ __forceinline__ int slot_of(const int* a, int n, int v, int none) {
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) pos += a[pos + s - 1] < v ? s : 0;
     return (pos < n && a[pos] == v) ? pos : none;
-}
-
-// Wave-level merging before the LDS atomic: neighbouring pixels mostly share a cell, so the wave walks its DISTINCT cells and
-// one lane adds the number of lanes that hold each (a same-address LDS atomic from 64 lanes would serialise instead).
-__device__ __forceinline__ void hist_add(int* hist, int key, bool valid) {
-    unsigned long long todo = __ballot(valid);
-    while (todo) {                                                        // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const int k0 = __shfl(key, leader, 64);
-        const unsigned long long same = __ballot(valid && key == k0) & todo;
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(hist + k0, __popcll(same));
-        todo &= ~same;
-    }
 }
 
 struct OverlapP {
@@ -143,7 +84,7 @@ __global__ __launch_bounds__(256) void instance_overlap_kernel(const OverlapP p)
     const int y0 = strip * p.rows, y1 = min(y0 + p.rows, p.H);
     const int Wv = (p.W + VEC - 1) / VEC;                                // VEC = 4 only when W % 4 == 0
     const int items = (y1 - y0) * Wv;
-    const int rounds = (items + 255) / 256;                              // whole waves stay in the loop: hist_add is wave-wide
+    const int rounds = (items + 255) / 256;                              // whole waves stay in the loop (wave_merge_add)
     for (int r = 0; r < rounds; ++r) {
         const int i = r * 256 + tid;
         const bool live = i < items;
@@ -193,7 +134,7 @@ __global__ __launch_bounds__(256) void instance_overlap_kernel(const OverlapP p)
             for (int e = 0; e < VEC; ++e) key[e] = 0;
         }
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) hist_add(hist, key[e], live);
+        for (int e = 0; e < VEC; ++e) wave_merge_add(hist, key[e], live);
     }
     __syncthreads();
     int* __restrict__ out = p.pairs + (long)plane * (M + 1) * (M + 1);
@@ -205,8 +146,6 @@ __global__ __launch_bounds__(256) void instance_overlap_kernel(const OverlapP p)
         }
     }
 }
-
-static inline bool link_aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 C2M_API int c2m_instance_overlap(const int32_t* ref, const int32_t* frame, const float* flow, const int32_t* ref_slots,
                                  const int32_t* ref_count, const int32_t* frame_slots, const int32_t* frame_count,
@@ -228,7 +167,7 @@ C2M_API int c2m_instance_overlap(const int32_t* ref, const int32_t* frame, const
     if ((long)P * strips >= (1L << 31)) return (int)hipErrorInvalidValue;
     const OverlapP p{ref, frame, flow, ref_slots, frame_slots, ref_count, frame_count, pairs, P, H, W, max_nodes, rows, strips};
     // plane bases are multiples of H * W words: 16-byte aligned for every plane when W % 4 == 0
-    const bool vec = W % 4 == 0 && link_aligned16(frame) && link_aligned16(flow);
+    const bool vec = W % 4 == 0 && c2m_aligned(16, frame, flow);
     const dim3 grid((unsigned)(P * strips));
     if (vec) hipLaunchKernelGGL(instance_overlap_kernel<4>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(instance_overlap_kernel<1>, grid, dim3(256), 0, s, p);

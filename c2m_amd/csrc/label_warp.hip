@@ -83,7 +83,6 @@ __global__ __launch_bounds__(256) void label_warp_kernel(const LabelWarpP p) {
     }
 }
 
-static inline bool aligned16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 C2M_API int c2m_label_warp(const float* flow, long sb, long sc, long st, const float* occ, float threshold, int fill_id,
                            const float* planes_f, int Cf, const int32_t* planes_i, int Ci, int B, int T, int H, int W,
@@ -97,8 +96,7 @@ C2M_API int c2m_label_warp(const float* flow, long sb, long sc, long st, const f
     const LabelWarpP p{flow, sb, sc, st, occ, threshold, (uint32_t)fill_id,
                        (const uint32_t*)planes_f, (uint32_t*)out_f, Cf, (const uint32_t*)planes_i, (uint32_t*)out_i, Ci,
                        B, T, H, W};
-    const bool vec = W % 4 == 0 && sb % 4 == 0 && sc % 4 == 0 && st % 4 == 0 && aligned16(flow) && aligned16(occ) &&
-                     aligned16(out_f) && aligned16(out_i);
+    const bool vec = W % 4 == 0 && sb % 4 == 0 && sc % 4 == 0 && st % 4 == 0 && c2m_aligned(16, flow, occ, out_f, out_i);
     // the largest tensor the kernel indexes with I is an output (the flow and occ offsets are 64-bit in either form)
     const bool small = px * (Cf > Ci ? Cf : Ci) < (1L << 31);
     const dim3 grid(c2m_grid(vec ? px / 4 : px, 256));

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void final_sum_kernel(const double* __restrict
     __shared__ double sm[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-    s = block_sum_256_d(s, sm);
+    s = block_sum_256(s, sm);
     if (threadIdx.x == 0) out[0] = (float)(s * scale);
 }
 
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void l1_partial_kernel(const T* __restrict__ a
         }
         s += fabsf(va - vb);
     }
-    const double bs = block_sum_256_d((double)s, sm);
+    const double bs = block_sum_256((double)s, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = bs;
 }
 
@@ -120,7 +120,7 @@ C2M_API int c2m_relu_tap_bwd(const void* y, const void* t, const void* gy, const
     C2M_ENTER();
     if (total <= 0) return 0;
     C2M_DISPATCH_DT(dt,
-        const bool vec = !(((uintptr_t)y | (uintptr_t)t | (uintptr_t)gy | (uintptr_t)out) & C2mVec4<T>::mask);
+        const bool vec = c2m_aligned(C2mVec4<T>::mask + 1, y, t, gy, out);
         const long n4 = vec ? total / 4 : 0;
         if (n4) hipLaunchKernelGGL(relu_tap_bwd_kernel<T>, dim3(c2m_grid(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)y,
                                    (const T*)t, (const T*)gy, gl, (T*)out, n4, total);
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const float* __restri
         const float v = (1.f - n / d) * 0.5f;
         s += fminf(fmaxf(v, 0.f), 1.f);
     }
-    const double bs = block_sum_256_d((double)s, sm);
+    const double bs = block_sum_256((double)s, sm);
     if (threadIdx.x == 0) part[blockIdx.x] = bs;
 }
 

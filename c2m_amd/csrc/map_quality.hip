@@ -10,7 +10,7 @@
 //
 //   mq_count_kernel  one pass over both maps, tiles of 2048 pixels of one image per workgroup (at most 1024 workgroups in all, each
 //                    walking its tiles with one LDS table).  A wave holds 64 consecutive pixels at a
-//                    time and walks its DISTINCT (gt key, pred key) pairs (the per-wave merge of panoptic.hip); the leader lane
+//                    time and walks its DISTINCT (gt key, pred key) pairs (the walk of wave_key_step, wave.h); the leader lane
 //                    of a pair adds the number of lanes that hold it to a 256-slot pair table in LDS.  After a barrier every
 //                    occupied slot is committed ONCE to the image's tables in global memory: confusion[pc][gc], area_g[g],
 //                    area_p[p], void_p[p] (g void), crowd_p[p] (g the crowd region of p's class) and, for a pair of equal class
@@ -149,6 +149,7 @@ __global__ __launch_bounds__(256) void mq_count_kernel(const MqP a) {
     }
 #pragma unroll
     for (int j = 0; j < C2M_MQ_PPT; ++j) {
+        // wave_key_step (wave.h) for two keys, written out: on the shared step this kernel's register allocation changes
         unsigned long long todo = __ballot(live[j]);
         while (todo) {                                                     // wave-uniform; every round clears at least one bit
             const int leader = __ffsll((long long)todo) - 1;
@@ -248,7 +249,7 @@ C2M_API int c2m_map_quality(const void* pred, const void* gt, int is_u8, const u
         return (int)hipErrorInvalidValue;
     const int K = num_classes * label_divisor;
     const MqWork w = mq_work(workspace, N, K, num_classes + 1, max_pairs);
-    if (workspace_bytes < w.bytes || (((uintptr_t)workspace) & 7)) return (int)hipErrorInvalidValue;
+    if (workspace_bytes < w.bytes || !c2m_aligned(8, workspace)) return (int)hipErrorInvalidValue;
     const long bpi = (HW + C2M_MQ_BLOCK_PIX - 1) / C2M_MQ_BLOCK_PIX;
     const int pb = (max_pairs + 255) / 256;
     if ((long)pb * N >= (1L << 31) || (long)N * num_classes >= (1L << 31)) return (int)hipErrorInvalidValue;

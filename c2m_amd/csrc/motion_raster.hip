@@ -144,7 +144,7 @@ __global__ __launch_bounds__(1024) void splat_scan_kernel(const int* __restrict_
     __shared__ int wsum[16];
     const long base = (long)blockIdx.x * HW;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool vec = (HW & 3) == 0 && ((((uintptr_t)(count + base)) | ((uintptr_t)(offset + base)) | ((uintptr_t)(cursor + base))) & 15) == 0;
+    const bool vec = (HW & 3) == 0 && c2m_aligned(16, count + base, offset + base, cursor + base);
     int carry = 0;
     for (int c0 = 0; c0 < HW; c0 += 4096) {
         const int i0 = c0 + (int)threadIdx.x * 4;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void norm_partial_kernel(const T* __restrict__
     const long end = beg + NORM_CHUNK < S ? beg + NORM_CHUNK : S;
     const T* __restrict__ p = x + plane * S;
     const int cnt = (int)(end - beg);
-    const bool vec = (S & 3) == 0 && ((uintptr_t)x & C2mVec4<T>::mask) == 0;      // chunk bounds are multiples of 4 then
+    const bool vec = (S & 3) == 0 && c2m_aligned(C2mVec4<T>::mask + 1, x);      // chunk bounds are multiples of 4 then
     float s = 0.f;
     // a chunk is at most 8 float4 per thread: they stay in registers for the second (centred) pass -- the first form read the
     // chunk twice (the second time from L2); same arithmetic in the same order, so the statistics keep their bits
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(256) void norm_apply_nc8_kernel(const ApplyP<bf16_t
 
 static inline bool norm_vec_ok(long S, const void* a, const void* b, const void* c, const void* d, int dt) {
     return S >= 1024 && (S & 3) == 0 &&
-           ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d)) & (dt == C2M_BF16 ? 7 : 15)) == 0;
+           c2m_aligned(dt == C2M_BF16 ? 8 : 16, a, b, c, d);
 }
 
 // y_nc8 (optional, bf16 tensors with S % 8 == 0 only): the same result in the channel-blocked layout of conv_nc8.hip as well.
@@ -326,7 +326,7 @@ C2M_API int c2m_norm_apply(const void* x, const float* mean, const float* invstd
     const long total = (long)N * C * S;
     if (total <= 0) return 0;
     if (y_nc8) {
-        if (dt != C2M_BF16 || (S & 7) || ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)gb) | ((uintptr_t)y_nc8)) & 15))
+        if (dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, y, gb, y_nc8))
             return (int)hipErrorInvalidValue;
         ApplyP<bf16_t> p{(const bf16_t*)x, mean, invstd, gamma, beta, (const bf16_t*)gb, (bf16_t*)y, N, C, S, mode, act, slope};
         const int CB = (C + 7) / 8;
@@ -544,7 +544,7 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_kernel(const BwdP<T> p) {
     const float mean = p.mean[st], invstd = p.invstd[st];
     const float ga = p.gamma ? p.gamma[c] : 1.f, be = p.gamma ? p.beta[c] : 0.f;
     float s1 = 0.f, s2 = 0.f;
-    const bool vec = (p.S & 3) == 0 && (((uintptr_t)p.x | (uintptr_t)p.gy | (uintptr_t)p.gb | (uintptr_t)p.ggb) & C2mVec4<T>::mask) == 0;
+    const bool vec = (p.S & 3) == 0 && c2m_aligned(C2mVec4<T>::mask + 1, p.x, p.gy, p.gb, p.ggb);
     if (vec) {                       // 16-byte accesses; element order inside a thread is fixed -> deterministic sums
         const T* __restrict__ xp = p.x + plane * p.S;
         const T* __restrict__ gp = p.gy + plane * p.S;
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(256) void norm_bwd_finalize_wave_kernel(const BwdP<
             s1 += a; s2 += b;
         }
     }
-    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    s1 = wave_sum(s1); s2 = wave_sum(s2);
     if (lane != 0) return;
     if (p.mode == 1) {
         const double cnt = (double)p.N * (double)p.S;
@@ -915,7 +915,7 @@ C2M_API int c2m_norm_bwd(const void* x, const void* gy, const float* mean, const
         p.dgamma = dgamma; p.dbeta = dbeta; p.dx = (T*)dx;
         p.N = N; p.C = C; p.S = S; p.mode = mode; p.act = act; p.slope = slope;
         if ((norm_fused_on & 1) && mode == 0 && !dgamma && !dx_nc8 && dx && vec && p.chunks == 1 &&
-            (!gb || ((((uintptr_t)gb) | ((uintptr_t)ggb)) & C2mVec4<T>::mask) == 0)) {
+            (!gb || c2m_aligned(C2mVec4<T>::mask + 1, gb, ggb))) {
             hipLaunchKernelGGL(norm_inst_bwd_fused_kernel<T>, dim3((unsigned)((long)N * C)), dim3(256), 0, s, p);
             return (int)hipGetLastError();
         }
@@ -936,7 +936,7 @@ C2M_API int c2m_norm_bwd(const void* x, const void* gy, const float* mean, const
         else
             hipLaunchKernelGGL(norm_bwd_apply_kernel<T>, dim3(c2m_grid(total, 256)), dim3(256), 0, s, p););
     if (dx_nc8) {
-        if (dt != C2M_BF16 || (S & 7) || ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)gb) | ((uintptr_t)dx) | ((uintptr_t)dx_nc8)) & 15))
+        if (dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, gy, gb, dx, dx_nc8))
             return (int)hipErrorInvalidValue;
         BwdP<bf16_t> p;
         p.x = (const bf16_t*)x; p.gy = (const bf16_t*)gy; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
@@ -982,8 +982,7 @@ __global__ void act_bwd_vec_kernel(const T* __restrict__ y, const T* __restrict_
 C2M_API int c2m_act_bwd(const void* y, const void* gy, void* gx, long total, int act, float slope, int dt, void* stream) {
     C2M_ENTER();
     if (total <= 0) return 0;
-    const uintptr_t mask = dt == C2M_BF16 ? 7 : 15;
-    const bool vec = (total & 3) == 0 && ((((uintptr_t)y) | ((uintptr_t)gy) | ((uintptr_t)gx)) & mask) == 0;
+    const bool vec = (total & 3) == 0 && c2m_aligned(dt == C2M_BF16 ? 8 : 16, y, gy, gx);
     C2M_DISPATCH_DT(dt,
         if (vec)
             hipLaunchKernelGGL(act_bwd_vec_kernel<T>, dim3(c2m_grid(total / 4, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -1048,7 +1047,7 @@ C2M_API int c2m_grad_to_nc8(int mode, const void* y, const void* t, const void* 
                             long S, long count, int act, float slope, void* stream) {
     C2M_ENTER();
     if (N <= 0 || C <= 0 || S <= 0) return 0;
-    if ((S & 7) || ((((uintptr_t)y) | ((uintptr_t)t) | ((uintptr_t)gy) | ((uintptr_t)g_nc8)) & 15) || (mode != 0 && mode != 1) ||
+    if ((S & 7) || !c2m_aligned(16, y, t, gy, g_nc8) || (mode != 0 && mode != 1) ||
         (mode == 0 && !gy) || (mode == 1 && (!t || !gl || count <= 0)))
         return (int)hipErrorInvalidValue;
     const int CB = (C + 7) / 8;

@@ -94,12 +94,13 @@ __global__ __launch_bounds__(256) void pan_candidates_kernel(const float* __rest
             for (int dy = -r; dy <= r; ++dy)
                 for (int dx = -r; dx <= r; ++dx) cand = cand && !(tile[(ly + r + dy) * LW + lx + r + dx] > v);
         }
-        const unsigned long long m = __ballot(cand);
-        if (m) {                                                          // wave-uniform
+        int found;
+        const int rank = wave_rank(cand, found);
+        if (found) {                                                      // wave-uniform
             int base = 0;
-            if (lane == 0) base = atomicAdd(cand_count + n, __popcll(m));
+            if (lane == 0) base = atomicAdd(cand_count + n, found);
             base = __shfl(base, 0, 64);
-            if (cand) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (y0 + ly) * W + x0 + lx;   // < H*W entries in all
+            if (cand) list[base + rank] = (y0 + ly) * W + x0 + lx;        // < H*W entries in all
         }
     }
 }
@@ -170,19 +171,6 @@ __global__ __launch_bounds__(1024) void pan_select_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ grouping
-// Wave-level merging before an integer atomic: neighbouring pixels mostly share a cell, so the wave walks its DISTINCT keys and
-// one lane adds the number of lanes that hold each.
-__device__ __forceinline__ void pan_hist_add(int* hist, int key, bool valid) {
-    unsigned long long todo = __ballot(valid);
-    while (todo) {                                                        // wave-uniform
-        const int leader = __ffsll((long long)todo) - 1;
-        const int k0 = __shfl(key, leader, 64);
-        const unsigned long long same = __ballot(valid && key == k0) & todo;
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(hist + k0, __popcll(same));
-        todo &= ~same;
-    }
-}
-
 struct PanGroupP {
     const float* logits; const uint8_t* labels;             // [N][C][H][W] fp32, or [N][H][W] labels (exactly one is set)
     const float* offset;                                    // [N][2][H][W] (dy, dx)
@@ -272,8 +260,8 @@ __global__ __launch_bounds__(256) void pan_group_kernel(const PanGroupP p) {
             p.semantic[q] = (uint8_t)sem[j];
             p.raw[q] = claimed ? bk[j] + 1 : 0;
         }
-        pan_hist_add(votes, bk[j] * p.T + ord[j] - 1, claimed);
-        pan_hist_add(s_area, sem[j], live[j] && !ord[j]);
+        wave_merge_add(votes, bk[j] * p.T + ord[j] - 1, claimed);         // every thread arrives here, live or not
+        wave_merge_add(s_area, sem[j], live[j] && !ord[j]);
     }
     __syncthreads();
     const int a = s_area[tid];
@@ -369,7 +357,7 @@ C2M_API int c2m_panoptic_maps(const float* logits, const uint8_t* labels, int C,
         !center_count || !workspace)
         return (int)hipErrorInvalidValue;
     const PanWork w = pan_work(workspace, N, HW, top_k, n_things);
-    if (workspace_bytes < w.words * 4 || (((uintptr_t)workspace) & 3)) return (int)hipErrorInvalidValue;
+    if (workspace_bytes < w.words * 4 || !c2m_aligned(4, workspace)) return (int)hipErrorInvalidValue;
     const int tiles_x = c2m_cdiv(W, C2M_PAN_TW), tiles_y = c2m_cdiv(H, C2M_PAN_TH);
     const long tiles = (long)tiles_x * tiles_y;
     const long bpi = (HW + C2M_PAN_BLOCK_PIX - 1) / C2M_PAN_BLOCK_PIX;

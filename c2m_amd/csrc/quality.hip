@@ -183,9 +183,9 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
         double e = (m0 ? sse0 : 0.0) + (m1 ? sse1 : 0.0);
         double s = (m0 ? ssim0 : 0.0) + (m1 ? ssim1 : 0.0);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-        e = wave_sum_d(e);
-        s = wave_sum_d(s);
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);   // (wave_sum(cnt) gets the k loop peeled)
+        e = wave_sum(e);
+        s = wave_sum(s);
         if (lane == 0) {
             red[wave][k * 4 + 0] = (double)(cnt & 0xffff);
             red[wave][k * 4 + 1] = e;

@@ -113,7 +113,6 @@ __global__ __launch_bounds__(256) void render_frames_kernel(const T* __restrict_
     }
 }
 
-static inline bool aligned_to(const void* q, uintptr_t bytes) { return (((uintptr_t)q) & (bytes - 1)) == 0; }
 static inline bool sheet_ok(const Sheet& s) {
     return s.B >= 0 && s.T >= 0 && s.H >= 0 && s.W >= 0 && s.rows >= 0 && s.cols >= 0 && (long)s.B <= (long)s.rows * s.cols &&
            (long)s.rows * s.H < (1L << 31) && (long)s.cols * s.W < (1L << 31);
@@ -128,7 +127,7 @@ C2M_API int c2m_render_frames(const void* x, int dt, int B, int C, int T, int H,
     const long px = sheet_pixels(s);
     if (px == 0) return 0;
     if (!out || (B > 0 && !x)) return (int)hipErrorInvalidValue;
-    const bool vec = W % 4 == 0 && aligned_to(out, 4) && aligned_to(x, dt == C2M_BF16 ? 8 : 16);
+    const bool vec = W % 4 == 0 && c2m_aligned(4, out) && c2m_aligned(dt == C2M_BF16 ? 8 : 16, x);
     const long items = vec ? px / 4 : px;
     const dim3 grid(c2m_grid(items, 256));
     hipStream_t st = (hipStream_t)stream;
@@ -255,8 +254,8 @@ C2M_API int c2m_render_flow(const void* flow, int dt, int B, int T, int H, int W
     if (!sheet_ok(s) || (mode != 0 && mode != 1) || (dt != C2M_F32 && dt != C2M_BF16)) return (int)hipErrorInvalidValue;
     const long px = sheet_pixels(s);
     if (px == 0) return 0;
-    if (!out || (B > 0 && !flow) || (mode == 0 && (!workspace || !aligned_to(workspace, 8)))) return (int)hipErrorInvalidValue;
-    const bool vec = W % 4 == 0 && aligned_to(out, 4) && aligned_to(flow, dt == C2M_BF16 ? 8 : 16);
+    if (!out || (B > 0 && !flow) || (mode == 0 && (!workspace || !c2m_aligned(8, workspace)))) return (int)hipErrorInvalidValue;
+    const bool vec = W % 4 == 0 && c2m_aligned(4, out) && c2m_aligned(dt == C2M_BF16 ? 8 : 16, flow);
     const long items = vec ? px / 4 : px;
     const dim3 grid(c2m_grid(items, 256));
     hipStream_t st = (hipStream_t)stream;
@@ -345,7 +344,7 @@ C2M_API int c2m_render_instances(const int32_t* ids, int B, int T, int H, int W,
     if (px == 0) return 0;
     if (!out || !palette || (B > 0 && !ids)) return (int)hipErrorInvalidValue;
     const InstP p{ids, base, out, palette, P, id_lo, id_hi, alpha};
-    const bool vec = W % 4 == 0 && aligned_to(out, 4) && aligned_to(base, 4);
+    const bool vec = W % 4 == 0 && c2m_aligned(4, out, base);
     const long items = vec ? px / 4 : px;
     const dim3 grid(c2m_grid(items, 256));
     if (vec) hipLaunchKernelGGL((render_instances_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, p, s, items);
@@ -393,15 +392,15 @@ __global__ __launch_bounds__(256) void draw_overlays_kernel(const OverlayP p, co
     if (threadIdx.x < 64) {                                       // wave 0: ordered compaction of the present boxes
         const int n = threadIdx.x;
         const bool present = n < p.N && p.presence[((long)b * p.N + n) * s.T + t] != 0;
-        const unsigned long long mask = __ballot(present);
+        int shown;
+        const int k = wave_rank(present, shown);
         if (present) {
-            const int k = __popcll(mask & ((1ull << n) - 1ull));
             const int32_t* q = p.boxes + (((long)b * p.N + n) * s.T + t) * 4;
             box[k][0] = q[0]; box[k][1] = q[1]; box[k][2] = q[2]; box[k][3] = q[3];
             const uint8_t* c = p.box_rgb + ((long)b * p.N + n) * 3;
             box_col[k] = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
         }
-        if (n == 0) nbox = __popcll(mask);
+        if (n == 0) nbox = shown;
     }
     __syncthreads();
     const int HW = s.H * s.W;                                     // a cell: below 2^31 pixels (checked by the host)

@@ -586,7 +586,7 @@ C2M_API int c2m_upsample2x_nc8(const void* in, void* out, long NCB, int Hi, int 
     C2M_ENTER();
     const long total = NCB * Hi * Wi;
     if (total <= 0) return 0;
-    if ((((uintptr_t)in) | ((uintptr_t)out)) & 15) return (int)hipErrorInvalidValue;
+    if (!c2m_aligned(16, in, out)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(upsample2x_nc8_kernel, dim3(c2m_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, (const uint4*)in,
                        (uint4*)out, NCB, Hi, Wi);
     return (int)hipGetLastError();
@@ -738,7 +738,7 @@ C2M_API int c2m_upsample2x_fwd(const void* in_, void* out_, long NC, int Hi, int
     C2M_ENTER();
     const long total = NC * Hi * Wi;
     if (total <= 0) return 0;
-    if ((((uintptr_t)out_) & 7) != 0) return resize_bilinear_launch(in_, out_, NC, Hi, Wi, 2 * Hi, 2 * Wi, 0, 2.0, dt, stream);
+    if (!c2m_aligned(8, out_)) return resize_bilinear_launch(in_, out_, NC, Hi, Wi, 2 * Hi, 2 * Wi, 0, 2.0, dt, stream);
     if (dt == C2M_BF16) {                  // same kernel on 2-byte elements: 4-byte stores of output pixel pairs
         const dim3 grid(c2m_grid(total, 256));
         if (total * 4 < (1L << 31)) hipLaunchKernelGGL((upsample2x_fwd_kernel<unsigned, bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in_, (bf16_t*)out_, NC, Hi, Wi);
@@ -755,7 +755,7 @@ C2M_API int c2m_upsample2x_bwd(const void* gout_, void* gin_, long NC, int Hi, i
     const long total = NC * Hi * Wi;
     if (total <= 0) return 0;
     if (dt == C2M_BF16) {
-        if (Wi >= 32 && Hi >= 8 && total * 4 < (1L << 31) && (((uintptr_t)gout_) & 3) == 0) {   // LDS-tiled form (fp32 window in LDS; 2-element loads)
+        if (Wi >= 32 && Hi >= 8 && total * 4 < (1L << 31) && c2m_aligned(4, gout_)) {   // LDS-tiled form (fp32 window in LDS; 2-element loads)
             const int tx = Wi >= 64 ? 64 : 32;
             const long tiles = (long)c2m_cdiv(Wi, tx) * c2m_cdiv(Hi, UB_TY) * NC;
             if (tiles < (1L << 31)) {
@@ -770,7 +770,7 @@ C2M_API int c2m_upsample2x_bwd(const void* gout_, void* gin_, long NC, int Hi, i
         return (int)hipGetLastError();
     }
     const float* gout = (const float*)gout_; float* gin = (float*)gin_;
-    if (Wi >= 32 && Hi >= 8 && total * 4 < (1L << 31) && (((uintptr_t)gout) & 7) == 0) {     // (2-element loads of the window)
+    if (Wi >= 32 && Hi >= 8 && total * 4 < (1L << 31) && c2m_aligned(8, gout)) {     // (2-element loads of the window)
         const int tx = Wi >= 64 ? 64 : 32;
         const long tiles = (long)c2m_cdiv(Wi, tx) * c2m_cdiv(Hi, UB_TY) * NC;
         if (tiles < (1L << 31)) {
@@ -783,7 +783,7 @@ C2M_API int c2m_upsample2x_bwd(const void* gout_, void* gin_, long NC, int Hi, i
             return (int)hipGetLastError();
         }
     }
-    if ((Wi & 1) == 0 && Wi >= 4 && ((((uintptr_t)gout) | ((uintptr_t)gin)) & 7) == 0) {
+    if ((Wi & 1) == 0 && Wi >= 4 && c2m_aligned(8, gout, gin)) {
         C2M_IDX_DISPATCH(total * 4, upsample2x_bwd_pair_kernel, dim3(c2m_grid(total / 2, 256)), (hipStream_t)stream, gout, gin, NC, Hi, Wi);
     } else {
         C2M_IDX_DISPATCH(total * 4, upsample2x_bwd_kernel, dim3(c2m_grid(total, 256)), (hipStream_t)stream, gout, gin, NC, Hi, Wi);
@@ -869,7 +869,7 @@ static int maxpool2x2_bwd_impl(const void* in_, const void* gout_, void* gin_, l
     const long total = NC * Hi * Wi;
     if (total <= 0) return 0;
     if (dt == C2M_BF16) {
-        if ((Hi & 1) == 0 && (Wi & 1) == 0 && ((((uintptr_t)in_) | ((uintptr_t)gin_)) & 3) == 0 && total < (1L << 31)) {
+        if ((Hi & 1) == 0 && (Wi & 1) == 0 && c2m_aligned(4, in_, gin_) && total < (1L << 31)) {
             hipLaunchKernelGGL((maxpool2_bwd_win_kernel<unsigned, bf16_t>), dim3(c2m_grid(total / 4, 256)), dim3(256), 0, (hipStream_t)stream,
                                (const bf16_t*)in_, (const bf16_t*)gout_, (bf16_t*)gin_, NC, Hi, Wi, relu);
             return (int)hipGetLastError();
@@ -880,7 +880,7 @@ static int maxpool2x2_bwd_impl(const void* in_, const void* gout_, void* gin_, l
         return (int)hipGetLastError();
     }
     const float* in = (const float*)in_; const float* gout = (const float*)gout_; float* gin = (float*)gin_;
-    if ((Hi & 1) == 0 && (Wi & 1) == 0 && ((((uintptr_t)in) | ((uintptr_t)gin)) & 7) == 0) {
+    if ((Hi & 1) == 0 && (Wi & 1) == 0 && c2m_aligned(8, in, gin)) {
         C2M_IDX_DISPATCH(total, maxpool2_bwd_win_kernel, dim3(c2m_grid(total / 4, 256)), (hipStream_t)stream, in, gout, gin, NC, Hi, Wi, relu);
         return (int)hipGetLastError();
     }

@@ -2517,14 +2517,26 @@ def _instance_input(instance, num_input_frames):
     return _f(instance if instance.dtype == torch.int32 else instance.to(torch.int32))
 
 
+def _id_range(id_range):
+    id_lo, id_hi = (int(v) for v in id_range)
+    if not 0 <= id_lo < id_hi:
+        raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
+    return id_lo, id_hi
+
+
+def _node_limits(min_pixels, max_nodes):
+    min_pixels, max_nodes = int(min_pixels), int(max_nodes)
+    if min_pixels < 1 or max_nodes < 1:
+        raise ValueError("min_pixels and max_nodes must be >= 1")
+    return min_pixels, max_nodes
+
+
 def instance_stats(instance, num_input_frames, id_range=(1000, 19000)):
     """Per-instance pixel statistics of the first `num_input_frames` frames: int32 [B, t_in, id_hi - id_lo, 5] on the device,
     (count, x_min, x_max, y_min, y_max) of every id in [id_lo, id_hi) (an absent id: count 0, x_min = y_min = 2**31 - 1,
     x_max = y_max = -1).  Integer atomics only: the table is the same on every run."""
     inst = _instance_input(instance, num_input_frames)
-    id_lo, id_hi = (int(v) for v in id_range)
-    if not 0 <= id_lo < id_hi:
-        raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
+    id_lo, id_hi = _id_range(id_range)
     B, T, H, W = inst.shape
     table = torch.empty(B, num_input_frames, id_hi - id_lo, 5, device=inst.device, dtype=torch.int32)
     _lib.check(_lib.lib().c2m_instance_stats(_p(inst), _p(table), B, T, num_input_frames, H, W, id_lo, id_hi, _stream()),
@@ -2542,9 +2554,7 @@ def instance_boxes(instance, num_input_frames, id_range=(1000, 19000), min_pixel
       ids [B, max_nodes] int32, boxes [B, max_nodes, t_in, 4] int32 (x_min, y_min, x_max + 1, y_max + 1: pixel edges),
       count [B] int32; slots past count[b] are zero.  More than `max_nodes` objects in a sample raises ValueError."""
     t_in = int(num_input_frames)
-    min_pixels, max_nodes = int(min_pixels), int(max_nodes)
-    if min_pixels < 1 or max_nodes < 1:
-        raise ValueError("min_pixels and max_nodes must be >= 1")
+    min_pixels, max_nodes = _node_limits(min_pixels, max_nodes)
     table = instance_stats(instance, t_in, id_range)
     B, nid = table.shape[0], table.shape[2]
     n_ids, n_box = B * max_nodes, B * max_nodes * t_in * 4
@@ -2566,9 +2576,7 @@ def instance_boxes(instance, num_input_frames, id_range=(1000, 19000), min_pixel
 
 # ---- linking the objects of two instance maps (csrc/instance_link.hip; c2m_amd.tracking is the public interface) ------------
 def _link_nodes(max_nodes, min_pixels=1):
-    max_nodes, min_pixels = int(max_nodes), int(min_pixels)
-    if min_pixels < 1 or max_nodes < 1:
-        raise ValueError("min_pixels and max_nodes must be >= 1")
+    min_pixels, max_nodes = _node_limits(min_pixels, max_nodes)
     cap = _lib.lib().c2m_instance_link_max_nodes()
     if max_nodes > cap:
         raise ValueError(f"max_nodes={max_nodes} is above the kernel cap of {cap} (one wave holds a plane's objects)")
@@ -2594,9 +2602,7 @@ def instance_slots(table, id_range=(1000, 19000), min_pixels=1, max_nodes=64):
     boxes [..., max_nodes, 4] pixel edges (x_min, y_min, x_max + 1, y_max + 1) and areas [..., max_nodes] (zero past count),
     count [...], overflow [...] (1: the plane holds more than max_nodes such ids; the rest is dropped).  Nothing is read back."""
     max_nodes, min_pixels = _link_nodes(max_nodes, min_pixels)
-    id_lo, id_hi = (int(v) for v in id_range)
-    if not 0 <= id_lo < id_hi:
-        raise ValueError(f"id_range must satisfy 0 <= lo < hi, got {id_range}")
+    id_lo, id_hi = _id_range(id_range)
     _hip_only(table, required=True)
     if table.dim() < 2 or tuple(table.shape[-2:]) != (id_hi - id_lo, 5):
         raise ValueError(f"table must be [..., {id_hi - id_lo}, 5] for id_range {id_range}, got {list(table.shape)}")

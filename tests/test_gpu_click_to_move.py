@@ -132,6 +132,41 @@ def test_instance_boxes_overflow_and_id_range():
         ops.instance_boxes(d, 2)                          # only one frame
 
 
+def test_instance_boxes_small_maps_many_objects():
+    """8 x 96 maps, three input frames, ids in [1000, 1600) at the first and last lane of a wave and of a 256-id chunk: 70
+    objects in sample 0 (max_nodes = 128: more than one wave of slots), the every-frame rule and the one-over-the-limit case."""
+    lo, hi, t_in, H, W = 1000, 1600, 3, 8, 96
+    rng = np.random.default_rng(9)
+    edges = [0, 63, 64, 255, 256, 257, 511, 512, 599]
+    gone, thin = 300, 301                                 # absent in frame 1; two pixels in frame 1 only
+    rest = np.setdiff1d(np.arange(hi - lo), edges + [gone, thin])
+    objects = [np.concatenate([edges, rng.choice(rest, 70 - len(edges), replace=False), [gone, thin]]), np.array([599, 5, 256])]
+    inst = np.array([0, 7, 999, 1600], np.int32)[rng.integers(0, 4, (2, t_in, H, W))]     # ids outside the range: ignored
+    for b, offs in enumerate(objects):
+        for cell, off in zip(rng.permutation(96), offs):  # 2 x 4 cells; frame t keeps 4 - t columns: 8, 6 and 4 pixels
+            r0, c0 = (cell // 24) * 2, (cell % 24) * 4
+            for t in range(t_in):
+                inst[b, t, r0:r0 + 2, c0:c0 + 4] = 0
+                if off == gone and t == 1:
+                    continue
+                inst[b, t, r0:r0 + (1 if off == thin and t == 1 else 2), c0:c0 + (2 if off == thin and t == 1 else 4 - t)] = lo + off
+    table = np_stats(inst, t_in, lo, hi)
+    d = torch.from_numpy(inst).to(DEV)
+    assert np.array_equal(ops.instance_stats(d, t_in, id_range=(lo, hi)).cpu().numpy(), table)
+    for min_pixels, kept in ((1, [71, 3]), (3, [70, 3])):
+        ids, boxes, count = ops.instance_boxes(d, t_in, id_range=(lo, hi), min_pixels=min_pixels, max_nodes=128)
+        w_ids, w_boxes, w_count = np_boxes(table, lo, min_pixels, 128)
+        assert w_count.tolist() == kept and np.array_equal(count.numpy(), w_count)
+        assert np.array_equal(ids.numpy(), w_ids) and np.array_equal(boxes.numpy(), w_boxes)
+        row = ids[0, :kept[0]].tolist()
+        assert lo + gone not in row and (lo + thin in row) == (min_pixels == 1)
+        assert set(lo + np.array(edges)) <= set(row) and ids[1, :3].tolist() == [lo + 5, lo + 256, lo + 599]
+    ids, boxes, count = ops.instance_boxes(d, t_in, id_range=(lo, hi), min_pixels=3, max_nodes=70)      # exactly at the limit
+    assert count.tolist() == [70, 3] and np.array_equal(ids.numpy(), np_boxes(table, lo, 3, 70)[0])
+    with pytest.raises(ValueError, match=r"\[0\].*max_nodes=69"):
+        ops.instance_boxes(d, t_in, id_range=(lo, hi), min_pixels=3, max_nodes=69)                       # one over
+
+
 # ------------------------------------------------------------------------------------------------ the tracker path
 # last-input-frame rectangles (id, x0, y0, x1, y1) at 128x256; input frame t sits (t_in - 1 - t) px further left
 RECTS = [[(11001, 20, 30, 60, 60), (13001, 100, 40, 130, 90), (18999, 180, 70, 220, 100)],

@@ -144,6 +144,46 @@ def test_slots_vs_numpy_and_instance_boxes(size, B, T):
         ops.instance_slots(table.long())
 
 
+def test_slots_on_a_table_at_wave_and_chunk_edges():
+    """A hand-made table of 600 ids (chunks of 256, 256 and 88 entries for the 256-thread workgroup) with qualifying ids at the
+    first and last lane of a wave and of a chunk; counts of 2 sit next to them, so min_pixels = 3 leaves them out."""
+    lo, nid, big = 1000, 600, np.iinfo(np.int32).max
+    edges = [0, 63, 64, 255, 256, 257, 511, 512, 599]
+    twos = [1, 62, 65, 254, 258, 510, 513, 598]
+    rng = np.random.default_rng(5)
+    rest = np.setdiff1d(np.arange(nid), edges + twos)
+    table = np.zeros((3, nid, 5), np.int32)
+    table[..., 1], table[..., 2], table[..., 3], table[..., 4] = big, -1, big, -1        # absent ids, as instance_stats leaves them
+    for p, n in ((0, 64), (1, 65)):                                  # plane 2 stays empty
+        big_ids = np.concatenate([edges, rng.choice(rest, n - len(edges), replace=False)])
+        table[p, big_ids, 0] = rng.integers(3, 900, n)
+        table[p, twos, 0] = 2
+        present = table[p, :, 0] > 0
+        k = int(present.sum())
+        x0, y0 = rng.integers(0, 100, k), rng.integers(0, 50, k)
+        table[p, present, 1], table[p, present, 2] = x0, x0 + rng.integers(0, 30, k)
+        table[p, present, 3], table[p, present, 4] = y0, y0 + rng.integers(0, 30, k)
+    d = dev(table)
+    for min_pixels in (1, 3):
+        slots, boxes, areas, count, overflow = (t.cpu().numpy() for t in
+                                                ops.instance_slots(d, id_range=(lo, lo + nid), min_pixels=min_pixels))
+        assert slots.shape == (3, M) and boxes.shape == (3, M, 4) and areas.shape == (3, M) and count.shape == (3,)
+        for p in range(3):
+            found = np.nonzero(table[p, :, 0] >= min_pixels)[0]      # ascending
+            keep = found[:M]
+            n, e = len(keep), table[p, keep].astype(np.int64)
+            assert count[p] == n and overflow[p] == (len(found) > M), (p, min_pixels)
+            assert np.array_equal(slots[p, :n], keep + lo) and (slots[p, n:] == -1).all()
+            assert np.array_equal(boxes[p, :n], np.stack([e[:, 1], e[:, 3], e[:, 2] + 1, e[:, 4] + 1], -1))
+            assert np.array_equal(areas[p, :n], e[:, 0]) and not boxes[p, n:].any() and not areas[p, n:].any()
+        if min_pixels == 3:
+            assert count.tolist() == [64, 64, 0] and overflow.tolist() == [0, 1, 0]
+            assert set(lo + np.array(edges)) <= set(slots[0].tolist()) and not set(lo + np.array(twos)) & set(slots[0].tolist())
+            assert slots[1, 0] == lo and slots[1, -1] < lo + 599     # the 65th id, the last of the table, is the one dropped
+        else:
+            assert count.tolist() == [64, 64, 0] and overflow.tolist() == [1, 1, 0]       # 72 and 73 ids
+
+
 def test_match_kernel_vs_host_rule():
     rng = np.random.default_rng(3)
     P = 48
