@@ -1,7 +1,7 @@
 // bf16 convolutions over CHANNEL-BLOCKED activations (round 4; BASELINE configs[2-4]).
 //
 // On NCHW the 8 consecutive input channels one lane of v_mfma_f32_32x32x16_bf16 consumes sit 2*H*W bytes apart, so the bf16
-// kernels of rounds 2-3 (conv_igemm.hip) gather 2 bytes per lane per load and run the matrix pipe 0.09-0.18 busy.  Here the
+// kernels of rounds 2-3 (conv_igemm.hip, conv_patch.hip, conv_wgrad.hip) gather 2 bytes per lane per load and run the matrix pipe 0.09-0.18 busy.  Here the
 // conv INPUT is "NC8": [N][ceil(C/8)][H][W][8] bf16 -- the 8 channels of one pixel are one 16-byte unit -- produced by
 // c2m_nchw_to_nc8 (one pass; fused into the producing kernels where they exist) and consumed by
 //
@@ -18,16 +18,10 @@
 #include "common.h"
 #include "dtype.h"
 #include "conv_store.h"
+#include "conv_types.h"
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define NC8_OOB 0x80000000u
 
 // ------------------------------------------------------------------------------------------------ NCHW -> NC8
 // out[n][cb][p][j] = in[n][cb*8 + j][p] (zeros for channels >= C).  A thread owns 8 consecutive pixels of one channel block:
@@ -81,7 +75,7 @@ struct Nc8P {
     const void* A;       // c2m_pack_weights_bf16_patch image: [chunk][tap 9][Mpad rows][2 halves] 16-byte units
     const void* X;       // NC8 activations
     float* Y;            // output (NCHW, fp32 or bf16), or the slab base when splits > 1
-    float* Y2;           // optional interior target of the reflect data gradient (ConvP semantics, conv_igemm.hip)
+    float* Y2;           // optional interior target of the reflect data gradient (ConvP semantics, conv_common.h)
     const float* bias;
     int M, Mpad, nchunks, CB;
     int Nimg, Ho, Wo, Hi, Wi;
@@ -153,7 +147,7 @@ __global__ __launch_bounds__(256, WGS) void conv_patch_nc8_kernel(const Nc8P p) 
     for (int i = 0; i < NAI; ++i) {
         const int d = (i * 4 + wave) * 64 + lane;
         const int tap = d / (2 * BM), half = (d / BM) & 1, row = d % BM;
-        avo[i] = d < A_UNITS ? (unsigned)(((tap * p.Mpad + m0 + row) * 2 + half) * 16) : NC8_OOB;
+        avo[i] = d < A_UNITS ? (unsigned)(((tap * p.Mpad + m0 + row) * 2 + half) * 16) : C2M_OOB;
     }
     const unsigned a_chunk_bytes = (unsigned)(NTAPS * p.Mpad * 32);
     // ---- patch DMA: wave w fetches rows j = 3 * (w & 1) .. + 2 of half plane w >> 1; unit u = j * 64 + lane -> patch pixel
@@ -175,7 +169,7 @@ __global__ __launch_bounds__(256, WGS) void conv_patch_nc8_kernel(const Nc8P p) 
                 ix = ix < 0 ? -ix : ix; ix = ix >= p.Wi ? 2 * p.Wi - 2 - ix : ix;
             }
             const bool ok = u < NPIX && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            pvo[par][r] = ok ? (unsigned)(iy * p.Wi + ix) * 16u : NC8_OOB;      // inside the plane; the plane rides in the scalar offset
+            pvo[par][r] = ok ? (unsigned)(iy * p.Wi + ix) * 16u : C2M_OOB;      // inside the plane; the plane rides in the scalar offset
         }
     // Every iteration issues exactly NDMA instructions per wave, so the counted waits below are constants: a chunk past the
     // split's end is "fetched" through zero-record descriptors (no memory traffic; zeros land in a buffer nobody reads again).
@@ -686,7 +680,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_nc8_kernel(const WgNc8P p) 
         for (int j = 0; j < 4; ++j) {
             const int I = wave * 4 + j, cb = I >> 1, r = (I & 1) * 2 + d_r;
             const bool ok = y0 + r < p.H && x0 + d_col < p.W;
-            const unsigned vo = ok ? ((unsigned)((ns * p.CBy + cby0 + cb) * p.T + tf) * HW16 + (unsigned)((y0 + r) * p.W + x0 + d_col) * 16u) : NC8_OOB;
+            const unsigned vo = ok ? ((unsigned)((ns * p.CBy + cby0 + cb) * p.T + tf) * HW16 + (unsigned)((y0 + r) * p.W + x0 + d_col) * 16u) : C2M_OOB;
             u32x4 rs = yrs;
             rs[2] = (live && cby0 + cb < p.CBy) ? p.dy_bytes : 0u;
             const unsigned dst = base + (unsigned)((cb * DPL + (I & 1) * 64) * 16);
@@ -705,7 +699,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_nc8_kernel(const WgNc8P p) 
                 ix = ix < 0 ? -ix : ix; ix = ix >= p.Win ? 2 * p.Win - 2 - ix : ix;
             }
             const bool ok = (x_code[j] >> 12) != 0 && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-            const unsigned vo = ok ? ((unsigned)((ns * p.CBx + cbx0 + xpl) * p.T + tx) * XHW16 + (unsigned)(iy * p.Win + ix) * 16u) : NC8_OOB;
+            const unsigned vo = ok ? ((unsigned)((ns * p.CBx + cbx0 + xpl) * p.T + tx) * XHW16 + (unsigned)(iy * p.Win + ix) * 16u) : C2M_OOB;
             u32x4 rs = xrs;
             rs[2] = (live && tok) ? p.x_bytes : 0u;
             const unsigned dst = base + (unsigned)((SD + I * 64) * 16);
@@ -968,7 +962,7 @@ __global__ __launch_bounds__(256, 2) void conv_s2_dgrad_nc8_kernel(const S2DgP p
         const int u = (pj0 + r) * 64 + lane;
         const int iy = q0 - 1 + u / PW, ix = p0 - 1 + u % PW;
         const bool ok = u < NPIX && (unsigned)iy < (unsigned)p.Ho && (unsigned)ix < (unsigned)p.Wo;      // dY outside its map: zeros
-        pvo[r] = ok ? (unsigned)n_img * (unsigned)p.CBy * plane_bytes + (unsigned)(iy * p.Wo + ix) * 16u : NC8_OOB;
+        pvo[r] = ok ? (unsigned)n_img * (unsigned)p.CBy * plane_bytes + (unsigned)(iy * p.Wo + ix) * 16u : C2M_OOB;
     }
     auto issue_dma = [&](int chunk, int buf, bool live) {
         const unsigned base = lds0 + (unsigned)(buf * BUF * 16);

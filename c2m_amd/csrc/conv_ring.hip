@@ -28,11 +28,8 @@
 // side) are loaded once per chunk into LDS -- every tap is the same slice read at another offset, the line ends are per-lane masks
 // -- and serve all the rows of the workgroup: 6-12x fewer line requests per CU.
 #include "common.h"
+#include "conv_types.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define RING_OOB 0x80000000u
 
 constexpr int RG_CK = 16;            // channels per chunk
 constexpr int RG_PX = 64;            // pixels (line positions x images) per workgroup of a row side; column sides: 32
@@ -161,12 +158,12 @@ __global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kern
     // loader roles: slice index x = 1 + (tid & 63) (pixel p0 + (tid & 63)) for the four channels 4 (tid >> 6) + e (wave-uniform);
     // the two neighbour elements x = 0 / 65 of channel tid & 15 by the first 32 threads
     auto slice_off = [&](long g) -> unsigned {
-        if (g < 0 || g >= npix) return RING_OOB;
+        if (g < 0 || g >= npix) return C2M_OOB;
         const int n = (int)(g / L), u = (int)(g - (long)n * L);
         return (unsigned)(((long)n * p.C * HW + lbase + (long)u * es) * 4);
     };
-    const unsigned voff_main = (tid & 63) < tpx ? slice_off(p0 + (tid & 63)) : RING_OOB;
-    const unsigned voff_halo = tid < 32 ? slice_off(tid < 16 ? p0 - 1 : p0 + tpx) : RING_OOB;
+    const unsigned voff_main = (tid & 63) < tpx ? slice_off(p0 + (tid & 63)) : C2M_OOB;
+    const unsigned voff_halo = tid < 32 ? slice_off(tid < 16 ? p0 - 1 : p0 + tpx) : C2M_OOB;
     const int cg = wave;                                      // = tid >> 6
     const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dY), 0, p.dy_bytes, 0x00020000);
     // MFMA roles: wave w owns the 32-row tiles t32 = (mg * 4 + w) * MTW + k, k < MTW, over both 32-pixel halves of the tile
@@ -200,12 +197,12 @@ __global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kern
             for (int e = 0; e < 4; ++e) {
                 if (p.diag & 4) break;
                 const int c = q * RG_CK + cg * 4 + e;         // wave-uniform; chunks past the end: c >= C -> zeros
-                sraw[sub][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsy, c < p.C ? voff_main : RING_OOB, c * HW * 4, 0));
+                sraw[sub][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsy, c < p.C ? voff_main : C2M_OOB, c * HW * 4, 0));
             }
             if (wave == 0 && !(p.diag & 4)) {
                 const int c = q * RG_CK + (tid & 15);
                 hraw[sub] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                    rsy, (c < p.C && voff_halo != RING_OOB) ? voff_halo + (unsigned)(c * HW * 4) : RING_OOB, 0, 0));
+                    rsy, (c < p.C && voff_halo != C2M_OOB) ? voff_halo + (unsigned)(c * HW * 4) : C2M_OOB, 0, 0));
             }
 #pragma unroll
             for (int k = 0; k < MTW; ++k) {

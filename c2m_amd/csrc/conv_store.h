@@ -1,4 +1,4 @@
-// Shared store epilogue of the MFMA convolution kernels (conv_igemm.hip, conv_nc8.hip).
+// Shared store epilogue of the MFMA convolution kernels (conv_igemm.hip, conv_gather.hip, conv_patch.hip, conv_nc8.hip).
 #pragma once
 #include "common.h"
 #include "dtype.h"

@@ -16,11 +16,8 @@
 // combination (over j) happens in registers, the row combination (over i = waves) through LDS in the epilogue, which also
 // applies bias + activation and writes coalesced NCHW rows.
 #include "common.h"
+#include "conv_types.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define WINO_OOB 0x80000000u
 
 struct WinoP {
     const float* U;      // packed filter transform (see wino_filter_kernel)
@@ -71,8 +68,6 @@ constexpr int PPOS = PH * PW;                // 180 patch positions per channel:
 constexpr int PCS = 192;                     // channel stride of the patch in LDS = three 64-lane DMA rows
 constexpr int PBUF = CKW * PCS;              // one patch buffer
 
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // v_pk_add_f32 with operand swizzles: p = (x0, x1), q = (x2, x3)
 static __device__ __forceinline__ f32x2 pk_a(f32x2 p, f32x2 q) {       // (x0 - x2, x1 + x2)
     f32x2 d;
@@ -149,7 +144,7 @@ __global__ __launch_bounds__(256, MT == 1 ? 3 : 2) void conv_wino_kernel(const W
             ix = ix < 0 ? -ix : ix; ix = ix >= p.Wi ? 2 * p.Wi - 2 - ix : ix;
         }
         const bool ok = pos < ppos && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-        pvo[sg] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : WINO_OOB;
+        pvo[sg] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : C2M_OOB;
     }
     // The LDS-DMA is issued through inline asm and TWO chunks ahead (three patch buffers).  hipcc makes the first MFMA
     // after an LDS-DMA wait until every VMEM operation older than the U-fragment loads has completed; with the builtin and
@@ -834,7 +829,7 @@ __global__ __launch_bounds__(256, NI == 1 ? (MI == 1 ? 3 : 2) : 1) void conv_win
     for (int i = 0; i < GY_UNITS; ++i) {
         const int u = tid + i * 256;
         const int co = u >> 3, row = (u >> 2) & 1, q = u & 3;
-        yvo[i] = m0 + co < p.M ? (unsigned)((m0 + co) * (int)p.cs + row * p.W + q * 4) * 4u : WINO_OOB;
+        yvo[i] = m0 + co < p.M ? (unsigned)((m0 + co) * (int)p.cs + row * p.W + q * 4) * 4u : C2M_OOB;
         ydst[i] = co * GY_STRIDE + row * GC + q * 4;
     }
     unsigned xbase[GX_UNITS]; int xdst[GX_UNITS], rowfix[GX_UNITS], cfix[GX_UNITS], tfix[GX_UNITS];
@@ -846,7 +841,7 @@ __global__ __launch_bounds__(256, NI == 1 ? (MI == 1 ? 3 : 2) : 1) void conv_win
         const int r = rem / 5, q = rem % 5;
         const bool live = u < GX_TOTAL && c0 + ci < p.K;
         const int kt = is3d ? (c0 + ci) / p.cin : 1, cch = is3d ? (c0 + ci) - kt * p.cin : c0 + ci;
-        xbase[i] = live ? (unsigned)((cch * (int)p.cs + (kt - 1) * HW + (r - 1) * p.W + 4 * q - 1) * 4) : WINO_OOB;
+        xbase[i] = live ? (unsigned)((cch * (int)p.cs + (kt - 1) * HW + (r - 1) * p.W + 4 * q - 1) * 4) : C2M_OOB;
         tfix[i] = (!live || !is3d) ? 0 : (kt == 0 ? 2 * HW * 4 : (kt == 2 ? -2 * HW * 4 : 0));   // frame -1 -> 1, frame T -> T-2
         rowfix[i] = !live ? 0 : (r == 0 ? 2 * p.W * 4 : (r == 3 ? -2 * p.W * 4 : 0));
         cfix[i] = !live ? 0 : (q == 0 ? 4 : (q == 4 ? -12 : 0));       // > 0: holds column -1;  < 0: holds column W
@@ -895,10 +890,10 @@ __global__ __launch_bounds__(256, NI == 1 ? (MI == 1 ? 3 : 2) : 1) void conv_win
                 if (first) vo += (unsigned)(tfix[i] > 0 ? tfix[i] : 0);
                 if (last) vo += (unsigned)(tfix[i] < 0 ? tfix[i] : 0);
             } else {
-                if (top) vo = rowfix[i] > 0 ? WINO_OOB : vo;
-                if (bot) vo = rowfix[i] < 0 ? WINO_OOB : vo;
-                if (first) vo = tfix[i] > 0 ? WINO_OOB : vo;
-                if (last) vo = tfix[i] < 0 ? WINO_OOB : vo;
+                if (top) vo = rowfix[i] > 0 ? C2M_OOB : vo;
+                if (bot) vo = rowfix[i] < 0 ? C2M_OOB : vo;
+                if (first) vo = tfix[i] > 0 ? C2M_OOB : vo;
+                if (last) vo = tfix[i] < 0 ? C2M_OOB : vo;
             }
             gx[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsx, vo, 0, 0));
         }

@@ -23,13 +23,8 @@
 // [xi][cout][tile] -> one thread per (cout, tile) computes A^T m A, adds the bias, applies the activation and stores four
 // 16-byte row segments (or per pixel into Y / Y_interior for the two-target data gradient of reflect-padded layers).
 #include "common.h"
+#include "conv_types.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define W4_OOB 0x80000000u
 
 struct Wino4P {
     const float* U;      // packed filter transform (wino4_filter_kernel)
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
     const unsigned long long t_begin = clock64();
 #endif
 #define sP (smem)                                              /* input patches [buf][k][18][34] (+pad): 60 KB, LDS-DMA two chunks ahead */
-#define sVo (reinterpret_cast<unsigned*>(smem + 3 * W4_PBUF))  /* per patch position: byte offset inside X or W4_OOB */
+#define sVo (reinterpret_cast<unsigned*>(smem + 3 * W4_PBUF))  /* per patch position: byte offset inside X or C2M_OOB */
 #define sV (smem + 3 * W4_PBUF + W4_TAB)                       /* V[buf][xi][k][tile]; reused by the epilogue */
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
                 ix = ix < 0 ? -ix : ix; ix = ix >= p.Wi ? 2 * p.Wi - 2 - ix : ix;
             }
             const bool ok = pos < W4_PPOS && c < W4_PW && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            sVo[pos] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : W4_OOB;
+            sVo[pos] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : C2M_OOB;
         }
     }
     __syncthreads();

@@ -138,7 +138,7 @@ C2M_API int c2m_correlation_fwd(const float* in1, const float* in2, float* out, 
 
 // ------------------------------------------------------------------------------------------------ bias + LeakyReLU
 // y = lrelu(x + bias[c]) in place: the epilogue of FlowNet2's transposed convolutions (submodules.py:75-80), whose matrix
-// part runs on the data-gradient kernels of conv_igemm.hip.
+// part runs on the data-gradient kernels behind c2m_conv_igemm (conv_igemm.hip and the files it routes to).
 __global__ void bias_act_kernel(float* __restrict__ x, const float* __restrict__ bias, long total, long HW, int C, int act,
                                 float slope) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {

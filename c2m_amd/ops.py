@@ -97,7 +97,7 @@ def _as(t, dtype):
 
 
 def _thin(M, splits, npix, two_target=False, ncls=1):
-    """The dispatch rule of c2m_conv_igemm for the <= 4-output-row vector-ALU kernels (conv_igemm.hip): those are fp32 in,
+    """The dispatch rule of c2m_conv_igemm for the <= 4-output-row vector-ALU kernels (conv_thin.hip): those are fp32 in,
     fp32 out in either precision mode, so the host must hand them fp32 tensors."""
     return M <= 4 and splits == 1 and npix >= 16384 and not two_target and ncls == 1
 
@@ -485,7 +485,7 @@ _NC8_VARIANT = int(os.environ.get("C2M_NC8_VARIANT", "0"))      # tile / bufferi
 # replays) it removes 77 of 174 layout passes (-0.95 ms) but the 8-channel x 8-pixel apply kernels run 2x as long as the per-plane
 # ones they replace (+1.2 ms): 47.7 vs 47.05 ms, 71.5 vs 70.7 ms.  Kept as an A/B knob with its tests (tests/test_gpu_nc8.py).
 _NC8_NORM = os.environ.get("C2M_NC8_NORM", "0") != "0"
-# NC8 gather kernel (conv_gather_nc8_kernel, conv_igemm.hip): every bf16 forward / data gradient the NC8 patch forms do not take
+# NC8 gather kernel (conv_gather_nc8_kernel, conv_gather.hip): every bf16 forward / data gradient the NC8 patch forms do not take
 _NC8_LOG = None
 _NC8_LOG_TAG = [""]          # (tools/nc8_producers.py: what made the gradient tensor a backward conversion sees)
 _NC8_GRAD = os.environ.get("C2M_NC8_GRAD", "1") != "0"      # act_bwd / tap backward write NC8 only where every reader is an NC8 kernel

@@ -34,7 +34,9 @@ int c2m_abi_version(void);
 int c2m_geom_len(void);
 int c2m_wino_geom_len(void);
 
-/* ---- convolution: implicit GEMM on v_mfma_f32_32x32x2_f32 (conv_igemm.hip) -------------------------------------
+/* ---- convolution: implicit GEMM on v_mfma_f32_32x32x2_f32 (conv_igemm.hip; kernel families behind the same entry points:
+ * conv_gather.hip, conv_patch.hip, conv_thin.hip; weight gradient conv_wgrad.hip, reflect fold conv_fold.hip, weight
+ * packing conv_pack.hip; NC8 / Winograd / ring forms in conv_nc8.hip, conv_wino.hip, conv_wino4.hip, conv_ring.hip) ----------
  * Replaces nn.Conv2d / nn.Conv3d (+ ReflectionPad2d/3d, bias, LeakyReLU/ReLU/Sigmoid) at:
  *   modules/layers/down_block.py:14-23,35-47   same_block.py:14-23,36-46,55-67   up_block.py:9-13
  *   residual_block.py:13-31,42-71   spade_block.py:47-49   vgg.py:92-137   generator/generator.py:76-78

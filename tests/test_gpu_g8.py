@@ -1,4 +1,4 @@
-"""The NC8 gather form of the bf16 forward / data-gradient kernels (conv_gather_nc8_kernel, conv_igemm.hip; round 4) against an fp32
+"""The NC8 gather form of the bf16 forward / data-gradient kernels (conv_gather_nc8_kernel, conv_gather.hip; round 4) against an fp32
 convolution of the same bf16-representable operands (every product exact in fp32: only the summation order differs): the layers the
 NC8 patch forms do not take -- (3,4,4) / (4,4,4) stride-2 3-D blocks, stride-2 2-D layers on small or odd maps, 3x3 on small maps,
 1x1, 7x7 --, stride-parity classes (batched and per class), the two-target reflect epilogue, split-K, ragged row / pixel tiles,

@@ -323,3 +323,36 @@ def test_build_tracks_the_public_header(monkeypatch):
     for target, deps in objects:
         assert os.path.samefile(_lib.HEADER, next(d for d in deps if d.endswith("c2m_hip.h"))), target
         assert any(d.endswith("c2m_geom.h") for d in deps) and any(d.endswith("common.h") for d in deps)
+
+
+def test_build_sources_exist_and_every_included_header_is_tracked(monkeypatch):
+    """build.SOURCES names real files, the convolution files share one set of flags, and every header a .hip file includes with
+    quotes -- directly or through another quoted include -- is a dependency of its object: a header missing from that list
+    would silently skip rebuilds (nothing is built here)."""
+    import re
+    for src in c2m_build.SOURCES:
+        assert os.path.isfile(os.path.join(c2m_build.CSRC, src)), src
+    conv = [src for src in c2m_build.SOURCES if src.startswith("conv_")]
+    assert "conv_igemm.hip" in conv
+    for src in conv:
+        assert c2m_build.SOURCES[src] == c2m_build.NOSLP, src
+
+    def quoted(path, found):
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), re.M):
+            header = os.path.realpath(os.path.join(os.path.dirname(path), inc))
+            assert os.path.isfile(header), f"{path} includes {inc}"
+            if header not in found:
+                found.add(header)
+                quoted(header, found)
+        return found
+
+    seen = {}
+    monkeypatch.setattr(c2m_build, "_stale", lambda target, deps: seen.__setitem__(target, list(deps)) or False)
+    monkeypatch.setattr(c2m_build.subprocess, "check_call", lambda *a, **k: pytest.fail("the test must not build"))
+    c2m_build.build()
+    for src in c2m_build.SOURCES:
+        obj = os.path.join(c2m_build.LIB_DIR, src.replace(".hip", ".o"))
+        tracked = {os.path.realpath(d) for d in seen[obj]}
+        assert os.path.realpath(os.path.join(c2m_build.CSRC, src)) in tracked, src
+        missing = quoted(os.path.join(c2m_build.CSRC, src), set()) - tracked
+        assert not missing, f"{src} includes headers build() does not track: {sorted(missing)}"

@@ -1,5 +1,5 @@
 """Round-3 hunt: conv_thin_wgrad_rows_kernel on a side stream next to the bf16 data-gradient kernels of the same layer (7x7
-RGB head, bf16 mode): slab entries differ from the sequential run when conv_igemm.hip is built WITH the SLP vectoriser; which of the
+RGB head, bf16 mode): slab entries differ from the sequential run when its file (conv_thin.hip) is built WITH the SLP vectoriser; which of the
 data-gradient launches disturbs it (answer: only c2m_conv_igemm's bf16 gather kernel).  c2m_amd/build.py builds that file without SLP."""
 import os, sys
 sys.path.insert(0, "/root/repo")

@@ -1,5 +1,5 @@
 """Register / LDS / scratch use of every kernel of one object file whose name contains a pattern.
-usage: python tools/isa_kernel.py conv_igemm conv_gather_nc8        (reads c2m_amd/lib/<file>.o; scratch under gpurun_out/isa_k)"""
+usage: python tools/isa_kernel.py conv_gather conv_gather_nc8      (reads c2m_amd/lib/<file>.o)"""
 import os
 import re
 import shutil
