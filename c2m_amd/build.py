@@ -22,6 +22,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_gather.hip": NOSLP, "conv_patch.hip": 
            "optim.hip": ["-ffp-contract=off"] + NOSLP, "data_prep.hip": ["-ffp-contract=off"] + NOSLP,
            "resize.hip": ["-ffp-contract=off"] + NOSLP,
            "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
+           "nearest_fill.hip": ["-ffp-contract=off"] + NOSLP,
            "detail_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,

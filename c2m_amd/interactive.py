@@ -24,7 +24,9 @@ frame, so the labels of frame t are the labels of the last input frame gathered 
 (ops.label_warp, HIP: the bilinear warp's own coordinates, nearest neighbour, nothing blended).  With them the output of
 one call is a complete input of the next, an object keeps its id across segments, and ops.instance_stats on the propagated
 ids gives the dragged object's boxes in the predicted frames (predicted_boxes, drag_error).  DESIGN.md, "Label propagation",
-has the coordinate rule and the ghost caveat of the sparse flow.
+has the coordinate rule and the ghost caveat of the sparse flow.  Where an object moved away the warp gathers the labels of the
+object that used to be there; occ_threshold with fill="nearest" gives such pixels the labels of the nearest visible background
+pixel instead (ops.nearest_fill, HIP).
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -262,8 +264,18 @@ def click_to_move(model, video, bg_mask, fg_mask, instance_mask, drags, input_of
 FLOW_OCC = {"dense_motion_bw": "occlusion_bw", "sparse_motion_bw": "sparse_occ_bw"}
 
 
+FILLS = (None, "nearest")
+
+
+def _check_fill(fill, occ_threshold):
+    if fill not in FILLS:
+        raise ValueError(f"fill must be one of {list(FILLS)}, got {fill!r}")
+    if fill is not None and occ_threshold is None:
+        raise ValueError(f"fill={fill!r} fills the pixels whose occlusion value is below occ_threshold: it needs occ_threshold")
+
+
 def propagate_maps(out, bg_mask, fg_mask, instance_mask, num_input_frames, flow="dense_motion_bw", occ_threshold=None,
-                   fill_id=0):
+                   fill_id=0, fill=None, id_range=(1000, 19000)):
     """Label maps of the predicted frames: the maps of input frame num_input_frames - 1 (no other frame is read) carried
     along the backward flow out[flow] by ops.label_warp -> dict(bg_mask [B,11,T,H,W], fg_mask [B,9,T,H,W] fp32, instance_mask
     [B,1,T,H,W] int32), on the device.
@@ -272,9 +284,17 @@ def propagate_maps(out, bg_mask, fg_mask, instance_mask, num_input_frames, flow=
     pixels; or "sparse_motion_bw", the rasterised object motion: exact for a rigid drag, but zero off the objects' new
     supports, so an object's id also stays at its OLD place (a ghost) wherever no other object's support covers it.
     occ_threshold: instance ids become fill_id where the matching occlusion map (occlusion_bw / sparse_occ_bw) is below
-    it -- a disoccluded pixel belongs to no known object; the semantic channels are left as gathered."""
+    it -- a disoccluded pixel belongs to no known object.  With fill=None the semantic channels of such a pixel stay as
+    gathered: they name the object that used to cover it.
+    fill: "nearest" (needs occ_threshold) gives every disoccluded pixel (a hole: occ < occ_threshold) ALL its label planes, the
+    20 semantic channels and the id, from the nearest pixel of the same frame that is visible and belongs to no object (a
+    seed: no hole, warped id outside id_range) -- ops.nearest_fill, HIP: exact Euclidean distance, ties to the smaller row,
+    then the smaller column.  A filled pixel carries its seed's stuff id, consistent with its one-hot channels; fill_id remains
+    the id of the holes of a frame that has no seed.  The dict then also holds unfilled [B,T] int32 on the device: the holes
+    each frame kept because it has no seed."""
     if flow not in FLOW_OCC:
         raise ValueError(f"flow must be one of {sorted(FLOW_OCC)}, got {flow!r}")
+    _check_fill(fill, occ_threshold)
     last = int(num_input_frames) - 1
     inst = instance_mask if instance_mask.dim() == 5 else instance_mask.unsqueeze(1)
     for name, t in (("bg_mask", bg_mask), ("fg_mask", fg_mask), ("instance_mask", inst)):
@@ -293,7 +313,14 @@ def propagate_maps(out, bg_mask, fg_mask, instance_mask, num_input_frames, flow=
     occ = None if occ_threshold is None else out[FLOW_OCC[flow]]
     with torch.no_grad():
         of, oi = ops.label_warp(f, planes_f, planes_i, occ, occ_threshold, fill_id)
-    return dict(bg_mask=of[:, :nbg], fg_mask=of[:, nbg:], instance_mask=oi)
+        maps = dict(bg_mask=of[:, :nbg], fg_mask=of[:, nbg:], instance_mask=oi)
+        if fill == "nearest":
+            id_lo, id_hi = (int(v) for v in id_range)
+            hole = occ[:, 0] < occ_threshold                       # the comparison label_warp's kernel makes on the same map
+            ids = oi[:, 0]
+            seed = ~hole & ((ids < id_lo) | (ids >= id_hi))
+            maps["unfilled"] = ops.nearest_fill(hole, seed, of, oi)
+    return maps
 
 
 def boxes_from_stats(rows):
@@ -429,19 +456,20 @@ def next_inputs(prev_inputs, out, maps, num_input_frames, flow_fn=None, needs_fl
 
 
 def continue_click_to_move(model, prev_inputs, out, drags, flow_fn=None, z_m=None, flow="dense_motion_bw",
-                           occ_threshold=None, **box_kw):
+                           occ_threshold=None, fill=None, **box_kw):
     """The next prediction from the previous one: drag again from where the objects now are.
 
     prev_inputs: dict(video, bg_mask, fg_mask, instance_mask) of the previous call (its first num_input_frames frames are
     read); out: what that call returned.  drags: in the coordinates of the LAST generated frame; the object under a click is
-    looked up in the propagated instance map, so it keeps the id it had in the first frame.  flow, occ_threshold:
-    propagate_maps; flow_fn: next_inputs (needed when the model reads input-frame flows, i.e. num_input_frames > 1; not
-    with the shipped num_input_frames: 1); z_m, box_kw: click_to_move.  common_params.scale_factor != 1 is not supported
-    yet (ValueError).  Returns (the dict of model.inference, the inputs it was called on: prev_inputs of the next call)."""
+    looked up in the propagated instance map, so it keeps the id it had in the first frame.  flow, occ_threshold, fill:
+    propagate_maps (box_kw's id_range, when given, is also its id_range); flow_fn: next_inputs (needed when the model reads
+    input-frame flows, i.e. num_input_frames > 1; not with the shipped num_input_frames: 1); z_m, box_kw: click_to_move.
+    common_params.scale_factor != 1 is not supported yet (ValueError).  Returns (the dict of model.inference, the inputs it
+    was called on: prev_inputs of the next call)."""
     _check_continuable(model)
     t_in = model.train_params["num_input_frames"]
     maps = propagate_maps(out, prev_inputs["bg_mask"], prev_inputs["fg_mask"], prev_inputs["instance_mask"], t_in, flow,
-                          occ_threshold)
+                          occ_threshold, fill=fill, id_range=box_kw.get("id_range", (1000, 19000)))
     with torch.no_grad():
         nxt = next_inputs(prev_inputs, out, maps, t_in, flow_fn, _reads_input_flows(model))
     return click_to_move(model, nxt["video"], nxt["bg_mask"], nxt["fg_mask"], nxt["instance_mask"], drags, nxt["input_of"],
@@ -449,7 +477,7 @@ def continue_click_to_move(model, prev_inputs, out, drags, flow_fn=None, z_m=Non
 
 
 def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=None, input_occ=None, flow_fn=None,
-            z_m=None, flow="dense_motion_bw", occ_threshold=None, **box_kw):
+            z_m=None, flow="dense_motion_bw", occ_threshold=None, fill=None, **box_kw):
     """A prediction of len(segments) * num_predicted_frames frames: click_to_move on the inputs, then
     continue_click_to_move on every result.
 
@@ -461,6 +489,9 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
       ids [K][B, N]: the objects each segment started with (ops.instance_boxes); boxes [K][B, N, T, 4], presence
       [K][B, N, T]: predicted_boxes of them in the segment's frames; targets [K]: drag_targets of the segment's drags;
       drag_errors [K]: drag_error of them.
+    fill="nearest" (with occ_threshold; propagate_maps): every disoccluded pixel of the propagated maps takes its labels from the
+    nearest visible background pixel, so the next segment is fed maps that agree with themselves; the dict then also holds
+    unfilled [B,K*T] int32 on the device, the holes each frame kept because it has no seed.
     A sample whose every object has left the frame (or is covered) ends the rollout with the "no object" ValueError of
     graph_from_boxes, prefixed with the segment.  Per segment the host reads what click_to_move reads plus the
     [B, N, T, 5] box table; frames and maps stay on the device."""
@@ -471,6 +502,7 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
         raise ValueError(f"z_m holds {len(z_m)} motion codes for {len(segments)} segments")
     if len(segments) > 1:
         _check_continuable(model)
+    _check_fill(fill, occ_threshold)
     tp = model.train_params
     t_in, T = tp["num_input_frames"], tp["num_predicted_frames"]
     id_range = box_kw.get("id_range", (1000, 19000))
@@ -488,7 +520,7 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
         except ValueError as e:
             raise ValueError(f"segment {k}: {e}") from e
         maps = propagate_maps(out, inputs["bg_mask"], inputs["fg_mask"], inputs["instance_mask"], t_in, flow,
-                              occ_threshold)
+                              occ_threshold, fill=fill, id_range=id_range)
         ids, boxes, presence = predicted_boxes(maps, info["ids"], id_range)
         res["outputs"].append(out)
         res["maps"].append(maps)
@@ -501,4 +533,6 @@ def rollout(model, video, bg_mask, fg_mask, instance_mask, segments, input_of=No
     res["generated"] = torch.cat([o["generated"] for o in res["outputs"]], 2)
     for key in ("bg_mask", "fg_mask", "instance_mask"):
         res[key] = torch.cat([m[key] for m in maps], 2)
+    if fill is not None:
+        res["unfilled"] = torch.cat([m["unfilled"] for m in maps], 1)
     return res

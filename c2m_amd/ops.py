@@ -2746,7 +2746,8 @@ def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fil
 
     flow [B,2,T,H,W] fp32 in pixels (a view with dense rows is read in place) or [B,2,H,W] (T = 1); planes_f [B,Cf,H,W] fp32,
     planes_i [B,Ci,H,W] int32, either may be None or have 0 channels.  occ [B,1,T,H,W] (or [B,1,H,W]) with `threshold`: where
-    occ < threshold the INTEGER outputs are `fill_id`; float planes are not touched.
+    occ < threshold the INTEGER outputs are `fill_id`; float planes are not touched there, so they name the object that used to
+    cover the pixel: nearest_fill (below) fills all planes of such pixels from the nearest visible background pixel.
     Returns (out_f [B,Cf,T,H,W] fp32 or None, out_i [B,Ci,T,H,W] int32 or None).  One launch, no atomics, no autograd."""
     _hip_only(flow, planes_f, planes_i, occ)
     B, T, H, W, Cf, Ci = _label_warp_plan(flow, planes_f, planes_i, occ, threshold)
@@ -2769,6 +2770,86 @@ def label_warp(flow, planes_f=None, planes_i=None, occ=None, threshold=None, fil
                                              _p(pi), Ci, B, T, H, W, _p(out_f) if Cf else None, _p(out_i) if Ci else None,
                                              _stream()), "label_warp")
     return out_f, out_i
+
+
+NEAREST_FILL_MAX_SIDE = 32768       # d^2 of two pixels then fits the upper half of the kernel's 64-bit key
+
+
+def _nearest_fill_plan(hole, seed, planes_f, planes_i):
+    """Every check of nearest_fill, made before anything is launched (host tensors pass: the device is the launch path's
+    check, all tensors on ONE device is checked here): (B, T, H, W, Cf, Ci)."""
+    for name, t in (("hole", hole), ("seed", seed)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"{name} must be a uint8 or bool mask, got {t.dtype}")
+        if t.dim() not in (3, 4):
+            raise ValueError(f"{name} must be [B,T,H,W] or [B,H,W], got {tuple(t.shape)}")
+    if hole.shape != seed.shape:
+        raise ValueError(f"hole {tuple(hole.shape)} and seed {tuple(seed.shape)} differ in shape")
+    B, (H, W) = hole.shape[0], hole.shape[-2:]
+    T = hole.shape[1] if hole.dim() == 4 else 1
+    if H > NEAREST_FILL_MAX_SIDE or W > NEAREST_FILL_MAX_SIDE or H * W >= 2 ** 31 or B * T >= 2 ** 31:
+        raise ValueError(f"{B * T} frames of {H}x{W} pixels: H and W must be at most {NEAREST_FILL_MAX_SIDE}, H * W and B * T "
+                         "below 2**31")
+    if planes_f is None and planes_i is None:
+        raise ValueError("nearest_fill needs planes_f or planes_i")
+    chans = []
+    for name, t, dtype in (("planes_f", planes_f, torch.float32), ("planes_i", planes_i, torch.int32)):
+        if t is None:
+            chans.append(0)
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.dim() != 5 or (t.shape[0], t.shape[2], t.shape[3], t.shape[4]) != (B, T, H, W):
+            raise ValueError(f"{name} must be [{B},C,{T},{H},{W}] for masks {tuple(hole.shape)}, got {tuple(t.shape)}")
+        if t.numel() and ((W > 1 and t.stride(4) != 1) or (H > 1 and t.stride(3) != W)):
+            raise ValueError(f"{name} must have dense rows (strides {W}, 1 of H, W), got strides {tuple(t.stride())}")
+        if any(t.shape[d] > 1 and t.stride(d) == 0 for d in (0, 1, 2)):
+            raise ValueError(f"{name} is filled in place: an expanded view (stride 0) would be written through several indices")
+        if t.device != hole.device:
+            raise ValueError(f"{name} is on {t.device} but the masks are on {hole.device}")
+        chans.append(t.shape[1])
+    if sum(chans) == 0:
+        raise ValueError("nearest_fill needs at least one plane (planes_f and planes_i have 0 channels)")
+    if seed.device != hole.device:
+        raise ValueError(f"hole and seed must be on one device, got {hole.device} and {seed.device}")
+    return B, T, H, W, chans[0], chans[1]
+
+
+def nearest_fill(hole, seed, planes_f=None, planes_i=None):
+    """Every hole pixel takes all its label words from the nearest seed pixel of the same image, IN PLACE (csrc/nearest_fill.hip;
+    DESIGN.md 4.2k).  For a hole pixel (y, x) of image (b, t) the source is the seed pixel (y', x') of that image with the
+    smallest ((y - y')**2 + (x - x')**2, y', x'), compared as integers -- exact Euclidean distance, ties to the smaller row, then
+    to the smaller column -- and planes[b, c, t, y, x] = planes[b, c, t, y', x'] for every plane c.  Pixels that are no holes
+    are never written, pixels that are no seeds are never read as sources.
+
+    hole, seed: [B,T,H,W] uint8 or bool on the device ([B,H,W]: T = 1), nonzero = set.  A pixel set in BOTH is an error of the
+    caller that the host cannot see: the kernel treats it as a hole and never as a seed.  planes_f [B,Cf,T,H,W] fp32, planes_i
+    [B,Ci,T,H,W] int32 (what label_warp returns): views with any batch, channel and frame strides and dense rows; either may be
+    None or have 0 channels, not both.  Planes are moved as 32-bit words, so every bit pattern survives (NaN payloads, negative
+    ids).  Returns unfilled [B,T] int32 on the device: the hole pixels of an image left untouched because the image has no seed.
+    Two zero-fills and two launches on the current stream; nothing is copied to the host and nothing synchronises."""
+    _hip_only(hole, seed, planes_f, planes_i)
+    B, T, H, W, Cf, Ci = _nearest_fill_plan(hole, seed, planes_f, planes_i)
+    _on_current_device(hole, seed, planes_f, planes_i)
+    dev = hole.device
+    as_u8 = lambda m: _f(m.detach().view(torch.uint8) if m.dtype == torch.bool else m.detach())
+    hole, seed = as_u8(hole), as_u8(seed)
+    unfilled = torch.empty(B, T, device=dev, dtype=torch.int32)
+    if B * T:
+        L = _lib.lib()
+        nbytes = L.c2m_nearest_fill_workspace_bytes(B, T, H, W)
+        if nbytes < 0:
+            raise ValueError(f"nearest_fill: sizes out of range (B={B}, T={T}, H={H}, W={W})")
+        work = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.int64)
+        pf = planes_f.detach() if Cf else None
+        pi = planes_i.detach() if Ci else None
+        fs = (pf.stride(0), pf.stride(1), pf.stride(2)) if Cf else (0, 0, 0)
+        si = (pi.stride(0), pi.stride(1), pi.stride(2)) if Ci else (0, 0, 0)
+        _lib.check(L.c2m_nearest_fill(_p(hole), _p(seed), _p(pf), *fs, Cf, _p(pi), *si, Ci, B, T, H, W, _p(unfilled), _p(work),
+                                      nbytes, _stream()), "nearest_fill")
+    return unfilled
 
 
 # ============================================================================ dataset-resolution output (csrc/detail_warp.hip)

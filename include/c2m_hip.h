@@ -352,6 +352,23 @@ int c2m_label_warp(const float* flow, long sb, long sc, long st, const float* oc
                    const float* planes_f, int Cf, const int32_t* planes_i, int Ci, int B, int T, int H, int W, float* out_f,
                    int32_t* out_i, void* stream);
 
+/* ---- nearest-seed fill of label planes (nearest_fill.hip): propagate_maps(fill="nearest") of c2m_amd.interactive ------------
+ * The reference has no counterpart.  hole, seed: uint8 [B][T][H][W], dense, nonzero = set; a pixel set in both is a hole and never
+ * a seed.  Every hole pixel (y, x) of image (b, t) takes the words planes[b][c][t][y'][x'] of every plane c from the seed pixel
+ * (y', x') of the same image with the smallest ((y - y')^2 + (x - x')^2, y', x'), compared as integers (exact; ties go to the
+ * smaller row, then the smaller column).  IN PLACE: only holes are written and only seeds are read, and the two are disjoint.
+ * planes_f fp32 [B][Cf][T][H][W] with element strides (fsb, fsc, fst) of sample, channel, frame and dense rows; planes_i int32
+ * likewise; words are copied, never interpreted.  Cf or Ci may be 0 (its pointer is then not read), not both.
+ * unfilled int32 [B][T] (zeroed by the call): the holes of an image WITHOUT a seed, which is left as it is.
+ * H, W <= 32768, H * W < 2^31.  workspace: c2m_nearest_fill_workspace_bytes(B, T, H, W) bytes (-1 for sizes out of range), 8-byte
+ * aligned, zero-filled by the call: one bit per pixel in 64-bit words per row, and a seed counter per image.  Everything is checked
+ * before the first launch; two zero-fills and two kernels on `stream`, no synchronisation, no copy to the host, no loop that waits
+ * for another wave (each is bounded by H or by ceil(W / 64)).  Integer atomic adds only: bit-repeatable.                        */
+long c2m_nearest_fill_workspace_bytes(int B, int T, int H, int W);
+int c2m_nearest_fill(const uint8_t* hole, const uint8_t* seed, float* planes_f, long fsb, long fsc, long fst, int Cf,
+                     int32_t* planes_i, long isb, long isc, long ist, int Ci, int B, int T, int H, int W, int32_t* unfilled,
+                     void* workspace, long workspace_bytes, void* stream);
+
 /* ---- predicted frames at dataset resolution (detail_warp.hip): c2m_amd.fullres ---------------------------------------------
  * The reference has no counterpart.  frame [B][H][W][3] uint8 is the last input frame at the output size; generated, warped
  * [B][3][T][h][w], flow [B][2][T][h][w] (working-size pixels) and occ [B][1][T][h][w] (NULL: 1 everywhere) are dense fp32 at the
