@@ -74,10 +74,19 @@ __global__ __launch_bounds__(256) void norm_partial_kernel(const T* __restrict__
     }
 }
 
+// Unbiased variance for the running statistics.  `rep`: the batch stands for `rep` identical copies of itself (a source frame
+// encoded once for `rep` predicted frames): mean and biased variance of the copies are the batch's own, only Bessel's factor sees
+// the larger count, m2 * rep / (n * rep - 1).  rep = 1 is m2 / (n - 1) bit for bit (both products are exact).
+__device__ inline double norm_unbiased_var(double m2, double n, double var, int rep) {
+    const double nr = n * (double)rep;
+    return nr > 1.0 ? m2 * (double)rep / (nr - 1.0) : var;
+}
+
 // one thread per statistic (plane for mode 0, channel for mode 1)
 __global__ void norm_finalize_kernel(const float* __restrict__ partial, float* __restrict__ mean_out,
                                      float* __restrict__ invstd_out, float* __restrict__ running_mean,
-                                     float* __restrict__ running_var, NormShape sh, float eps, float momentum) {
+                                     float* __restrict__ running_var, NormShape sh, float eps, float momentum,
+                                     int rep) {
     const int nstat = sh.mode == 0 ? sh.N * sh.C : sh.C;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nstat) return;
@@ -101,7 +110,7 @@ __global__ void norm_finalize_kernel(const float* __restrict__ partial, float* _
     mean_out[i] = (float)mean;
     invstd_out[i] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
-        const double unbiased = n > 1.0 ? m2 / (n - 1.0) : var;
+        const double unbiased = norm_unbiased_var(m2, n, var, rep);
         running_mean[i] = (float)((1.0 - momentum) * running_mean[i] + momentum * mean);
         running_var[i] = (float)((1.0 - momentum) * running_var[i] + momentum * unbiased);
     }
@@ -115,7 +124,7 @@ __global__ __launch_bounds__(256) void norm_finalize_bn_kernel(const float* __re
                                                                float* __restrict__ invstd_out,
                                                                float* __restrict__ running_mean,
                                                                float* __restrict__ running_var, NormShape sh, float eps,
-                                                               float momentum) {
+                                                               float momentum, int rep) {
     const int lane = threadIdx.x & 63;
     const int ch = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ch >= sh.C) return;                                   // wave-uniform
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(256) void norm_finalize_bn_kernel(const float* __re
     mean_out[ch] = (float)mean;
     invstd_out[ch] = (float)(1.0 / sqrt(var + (double)eps));
     if (running_mean) {
-        const double unbiased = n > 1.0 ? m2 / (n - 1.0) : var;
+        const double unbiased = norm_unbiased_var(m2, n, var, rep);
         running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
         running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unbiased);
     }
@@ -156,10 +165,12 @@ __global__ __launch_bounds__(256) void norm_finalize_bn_kernel(const float* __re
 
 C2M_API long c2m_norm_workspace_floats(int N, int C, long S) { return (long)N * C * norm_chunks(S) * 4; }
 
-C2M_API int c2m_norm_stats(const void* x, float* mean, float* invstd, float* running_mean, float* running_var,
-                           float* workspace, int N, int C, long S, int mode, float eps, float momentum, int dt, void* stream) {
+C2M_API int c2m_norm_stats_rep(const void* x, float* mean, float* invstd, float* running_mean, float* running_var,
+                               float* workspace, int N, int C, long S, int mode, float eps, float momentum, int rep, int dt,
+                               void* stream) {
     C2M_ENTER();
     if ((long)N * C * S <= 0) return 0;
+    if (rep < 1 || (mode == 0 && rep != 1)) return (int)hipErrorInvalidValue;
     NormShape sh{N, C, S, mode, norm_chunks(S)};
     hipStream_t s = (hipStream_t)stream;
     C2M_DISPATCH_DT(dt, hipLaunchKernelGGL(norm_partial_kernel<T>, dim3((unsigned)((long)N * C * sh.chunks)), dim3(256), 0, s,
@@ -167,11 +178,16 @@ C2M_API int c2m_norm_stats(const void* x, float* mean, float* invstd, float* run
     const int nstat = mode == 0 ? N * C : C;
     if (mode == 1 && N * sh.chunks >= 16)
         hipLaunchKernelGGL(norm_finalize_bn_kernel, dim3(c2m_cdiv(C, 4)), dim3(256), 0, s, workspace, mean, invstd,
-                           running_mean, running_var, sh, eps, momentum);
+                           running_mean, running_var, sh, eps, momentum, rep);
     else
         hipLaunchKernelGGL(norm_finalize_kernel, dim3(c2m_cdiv(nstat, 128)), dim3(128), 0, s, workspace, mean, invstd,
-                           running_mean, running_var, sh, eps, momentum);
+                           running_mean, running_var, sh, eps, momentum, rep);
     return (int)hipGetLastError();
+}
+
+C2M_API int c2m_norm_stats(const void* x, float* mean, float* invstd, float* running_mean, float* running_var,
+                           float* workspace, int N, int C, long S, int mode, float eps, float momentum, int dt, void* stream) {
+    return c2m_norm_stats_rep(x, mean, invstd, running_mean, running_var, workspace, N, C, S, mode, eps, momentum, 1, dt, stream);
 }
 
 // ------------------------------------------------------------------------------------------- apply (forward)
@@ -420,7 +436,8 @@ __global__ __launch_bounds__(256) void norm_inst_fused_kernel(const ApplyP<T> p,
 template <class T, int NE>
 __global__ __launch_bounds__(256) void norm_bn_small_fused_kernel(const ApplyP<T> p, float* __restrict__ mean_out,
                                                                   float* __restrict__ invstd_out, float* __restrict__ running_mean,
-                                                                  float* __restrict__ running_var, float eps, float momentum) {
+                                                                  float* __restrict__ running_var, float eps, float momentum,
+                                                                  int rep) {
     __shared__ float sm[4];
     const int c = blockIdx.x;
     const int S = (int)p.S, total = p.N * S;
@@ -455,7 +472,7 @@ __global__ __launch_bounds__(256) void norm_bn_small_fused_kernel(const ApplyP<T
     if (threadIdx.x == 0) {
         mean_out[c] = mean; invstd_out[c] = invstd;
         if (running_mean) {
-            const double unbiased = total > 1 ? (double)m2 / (double)(total - 1) : var;
+            const double unbiased = norm_unbiased_var((double)m2, (double)total, var, rep);
             running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * (double)mean);
             running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
         }
@@ -479,11 +496,13 @@ C2M_API int c2m_norm_set_fused(int mask) { const int old = norm_fused_on; norm_f
 
 // Statistics + apply in one call (c2m_norm_stats followed by c2m_norm_apply, without the NC8 side output): instance-norm planes of
 // 1024 ... 32768 elements take the one-launch kernel above, everything else the three launches.
-C2M_API int c2m_norm_fwd(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
-                         const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode,
-                         float eps, float momentum, int act, float slope, int dt, void* stream) {
+// `rep` (batch statistics only): the running variance is updated as if the batch were `rep` copies of itself, see norm_unbiased_var.
+C2M_API int c2m_norm_fwd_rep(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
+                             const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode,
+                             float eps, float momentum, int rep, int act, float slope, int dt, void* stream) {
     C2M_ENTER();
     if ((long)N * C * S <= 0) return 0;
+    if (rep < 1 || (mode == 0 && rep != 1)) return (int)hipErrorInvalidValue;
     if ((norm_fused_on & 1) && mode == 0 && S <= 32768 && norm_vec_ok(S, x, y, gb, nullptr, dt)) {
         C2M_DISPATCH_DT(dt,
             ApplyP<T> p{(const T*)x, mean, invstd, gamma, beta, (const T*)gb, (T*)y, N, C, S, mode, act, slope};
@@ -500,14 +519,21 @@ C2M_API int c2m_norm_fwd(const void* x, float* mean, float* invstd, float* runni
         C2M_DISPATCH_DT(dt,
             ApplyP<T> p{(const T*)x, mean, invstd, gamma, beta, nullptr, (T*)y, N, C, S, mode, act, slope};
             if (tot <= 2048)
-                hipLaunchKernelGGL((norm_bn_small_fused_kernel<T, 8>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, p, mean, invstd, running_mean, running_var, eps, momentum);
+                hipLaunchKernelGGL((norm_bn_small_fused_kernel<T, 8>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, p, mean, invstd, running_mean, running_var, eps, momentum, rep);
             else
-                hipLaunchKernelGGL((norm_bn_small_fused_kernel<T, 32>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, p, mean, invstd, running_mean, running_var, eps, momentum););
+                hipLaunchKernelGGL((norm_bn_small_fused_kernel<T, 32>), dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, p, mean, invstd, running_mean, running_var, eps, momentum, rep););
         return (int)hipGetLastError();
     }
-    const int rc = c2m_norm_stats(x, mean, invstd, running_mean, running_var, workspace, N, C, S, mode, eps, momentum, dt, stream);
+    const int rc = c2m_norm_stats_rep(x, mean, invstd, running_mean, running_var, workspace, N, C, S, mode, eps, momentum, rep, dt, stream);
     if (rc) return rc;
     return c2m_norm_apply(x, mean, invstd, gamma, beta, gb, y, nullptr, N, C, S, mode, act, slope, dt, stream);
+}
+
+C2M_API int c2m_norm_fwd(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
+                         const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode,
+                         float eps, float momentum, int act, float slope, int dt, void* stream) {
+    return c2m_norm_fwd_rep(x, mean, invstd, running_mean, running_var, workspace, gamma, beta, gb, y, N, C, S, mode, eps, momentum, 1,
+                            act, slope, dt, stream);
 }
 
 // ------------------------------------------------------------------------------------------- backward

@@ -88,20 +88,31 @@ class OcclusionAwareGenerator(nn.Module):
     def get_cond_maps(self, label):
         return [[m] for m in self.flowembedder(label)]
 
-    def forward(self, first_frame, flow, occlusion_map):
-        nd = self.num_down_blocks
+    def forward(self, first_frame, flow, occlusion_map, source_repeats=1):
+        """source_repeats = T: first_frame holds the B distinct source frames, flow and occlusion_map the T*B predicted frames
+        (frame-major, fold_time's order).  Everything that sees first_frame alone -- first, down_blocks and, with SPADE, middle --
+        then runs on B images and is expanded to T*B where flow and occlusion enter; its BatchNorms count the copies in their running
+        variance (rep), and the backward of the expand sums the T gradients.  1: first_frame is [T*B] itself (the reference)."""
+        nd, T = self.num_down_blocks, int(source_repeats)
+        if T < 1 or flow.shape[0] != T * first_frame.shape[0]:
+            raise ValueError(f"generator: {first_frame.shape[0]} source frames x {T} repeats vs {flow.shape[0]} flow frames")
+        frames = first_frame if T == 1 else _repeat_frames(first_frame, T)       # the 3-channel image, where a warp reads it
         if self.use_spade:
-            img_warp = ops.flow_warp(first_frame, flow)
+            img_warp = ops.flow_warp(frames, flow)
             cond = self.get_cond_maps(torch.cat([img_warp, flow, occlusion_map], dim=1))
         out = self.first(first_frame)
         for blk in self.down_blocks:
-            out = blk(out)
+            out = blk(out, rep=T)
         if not self.use_spade:
+            if T != 1:
+                out = _repeat_frames(out, T)
             out = self.apply_optical(input_ref=out, optical_flow=flow, occlusion_map=occlusion_map)
         for blk in self.middle:
-            out = blk(out)
+            out = blk(out, rep=T if self.use_spade else 1)
+        if self.use_spade and T != 1:
+            out = _repeat_frames(out, T)
         if "kitti" in self.dataset:
-            xw = self.first_warped(ops.flow_warp(first_frame, flow))
+            xw = self.first_warped(ops.flow_warp(frames, flow))
             for blk in self.down_blocks_warped:
                 xw = blk(xw)
             occ = occlusion_map
@@ -119,6 +130,12 @@ class OcclusionAwareGenerator(nn.Module):
         if out.shape[-2:] != first_frame.shape[-2:]:            # to the frame size before the 7x7 head (generator.py:155-156)
             out = ops.resize_bilinear_grad(out, first_frame.shape[-2:])
         return conv_module(out, self.final[0], act="sigmoid")
+
+
+def _repeat_frames(x, t):
+    """[B,...] -> [t*B,...], frame-major like fold_time.  Backward: autograd's sum over the repeat axis (one ATen reduction in a
+    fixed order: bit-repeatable from step to step)."""
+    return x.unsqueeze(0).expand(t, *x.shape).reshape(t * x.shape[0], *x.shape[1:])
 
 
 def _resize_with_grad(x, size):

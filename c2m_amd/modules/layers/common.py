@@ -71,9 +71,10 @@ def feeds_conv(conv, padding=None, padding_mode=None):
     return ops.conv_consumer(conv.weight, tuple(conv.stride), tuple(pad) if not isinstance(pad, int) else pad, mode, conv.bias)
 
 
-def batch_norm_module(x, bn, act=None, feeds=None, private_input=False):
+def batch_norm_module(x, bn, act=None, feeds=None, private_input=False, rep=1):
     """nn.BatchNorm{1,2,3}d container, train mode: batch statistics + running-stat update, fused activation.
-    feeds: `feeds_conv(...)` when the result goes into exactly one convolution and nowhere else (ops.conv_consumer)."""
+    feeds: `feeds_conv(...)` when the result goes into exactly one convolution and nowhere else (ops.conv_consumer).
+    rep: x stands for `rep` identical copies of itself (ops.batch_norm_act); the running variance counts them."""
     if bn.training:
         if not _defer_counters:
             bn.num_batches_tracked += 1
@@ -84,7 +85,7 @@ def batch_norm_module(x, bn, act=None, feeds=None, private_input=False):
             else:
                 ent[1] += 1
         return ops.batch_norm_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, act, bn.eps, bn.momentum, feeds,
-                                  private_input)
+                                  private_input, rep)
     # eval: running statistics (inference path) -- scale/shift folded into the same apply kernel
     invstd = torch.rsqrt(bn.running_var + bn.eps)
     return ops.norm_apply_eval(x, bn.running_mean, invstd, bn.weight, bn.bias, act)

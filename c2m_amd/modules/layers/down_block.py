@@ -15,10 +15,11 @@ class DownBlock2d(nn.Module):
         self.norm = nn.BatchNorm2d(out_features, affine=True)
         self.use_norm = use_norm
 
-    def forward(self, x):
+    def forward(self, x, rep=1):
+        """rep: x stands for `rep` copies of itself (batch_norm_module)."""
         if not self.use_norm:
             return conv_module(x, self.conv, act="lrelu")
-        return batch_norm_module(conv_module(x, self.conv), self.norm, act="lrelu", private_input=True)   # (the conv output is a temporary)
+        return batch_norm_module(conv_module(x, self.conv), self.norm, act="lrelu", private_input=True, rep=rep)   # (the conv output is a temporary)
 
 
 class DownBlock3d(nn.Module):

@@ -16,11 +16,13 @@ class ResidualBlock(nn.Module):
         self.norm2 = nn.BatchNorm2d(out_planes, affine=True)
         self._pad = padding
 
-    def forward(self, x):
+    def forward(self, x, rep=1):
+        # rep: x stands for `rep` copies of itself (batch_norm_module)
         # (each norm result is read by the convolution behind it and by nothing else: feeds -> NC8-only output where that pays)
-        out = batch_norm_module(x, self.norm1, act="relu", feeds=feeds_conv(self.conv1, self._pad, "reflect"))
+        out = batch_norm_module(x, self.norm1, act="relu", feeds=feeds_conv(self.conv1, self._pad, "reflect"), rep=rep)
         out = conv_module(out, self.conv1, padding=self._pad, padding_mode="reflect")
-        out = batch_norm_module(out, self.norm2, act="relu", feeds=feeds_conv(self.conv2, self._pad, "reflect"), private_input=True)
+        out = batch_norm_module(out, self.norm2, act="relu", feeds=feeds_conv(self.conv2, self._pad, "reflect"), private_input=True,
+                                rep=rep)
         out = conv_module(out, self.conv2, padding=self._pad, padding_mode="reflect")
         return out + x
 

@@ -141,10 +141,11 @@ class GeneratorFullModel(nn.Module):
         t_in, T = tp["num_input_frames"], tp["num_predicted_frames"]
         last = v["frames"][:, :, t_in - 1]
         b, c, h, w = last.shape
-        rep = last.unsqueeze(0).expand(T, b, c, h, w).reshape(T * b, c, h, w)
-        gen = self.generator(rep, fold_time(out["dense_motion_bw"]), fold_time(out["occlusion_bw"]))
+        # the generator encodes the b distinct source frames once and repeats the features where flow and occlusion enter
+        gen = self.generator(last, fold_time(out["dense_motion_bw"]), fold_time(out["occlusion_bw"]), source_repeats=T)
         out["generated"] = unfold_time(gen, T)
         with torch.no_grad():
+            rep = last.unsqueeze(0).expand(T, b, c, h, w).reshape(T * b, c, h, w)
             sparse = fold_time(out["sparse_motion_bw"])
             out["generated_sparse"] = unfold_time(ops.flow_warp(rep, sparse), T)
             out["generated_sparse_occ"] = unfold_time(ops.flow_warp(rep, sparse, fold_time(out["sparse_occ_bw"])), T)

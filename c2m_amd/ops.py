@@ -2107,8 +2107,11 @@ class _NormActFn(torch.autograd.Function):
     """y = act(norm(x) * scale + shift); mode 0 instance / 1 batch statistics; gb = SPADE [N,2C,...] map or None."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, gb, running_mean, running_var, mode, act, eps, momentum, feeds=None, private_input=False):
+    def forward(ctx, x, gamma, beta, gb, running_mean, running_var, mode, act, eps, momentum, feeds=None, private_input=False, rep=1):
         _dev(x, gamma, beta, gb)
+        rep = int(rep)
+        if rep < 1 or (rep != 1 and mode != 1):
+            raise ValueError(f"norm: replication count {rep} (batch statistics only, >= 1)")
         x = _f(x)
         ctx.gb_dtype = gb.dtype if gb is not None else None
         gb = _as(gb, x.dtype)                   # the SPADE map shares the activation type (bf16 on the bf16 data path)
@@ -2136,11 +2139,11 @@ class _NormActFn(torch.autograd.Function):
         yn = torch.empty((N, _cdiv(C, 8)) + tuple(x.shape[2:]) + (8,), device=x.device, dtype=BF16) if (ctx.nc8 or only) else None
         if yn is None:
             # statistics + apply in one call: instance-norm planes of <= 32768 elements run as ONE launch (norm_inst_fused_kernel)
-            _lib.check(L.c2m_norm_fwd(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), _p(gamma), _p(beta), _p(gb),
-                                      _p(y), N, C, S, mode, eps, momentum, ACT[act], LRELU_SLOPE, dt, _stream()), "norm_fwd")
+            _lib.check(L.c2m_norm_fwd_rep(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), _p(gamma), _p(beta), _p(gb),
+                                          _p(y), N, C, S, mode, eps, momentum, rep, ACT[act], LRELU_SLOPE, dt, _stream()), "norm_fwd")
         else:
-            _lib.check(L.c2m_norm_stats(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), N, C, S, mode,
-                                        eps, momentum, dt, _stream()), "norm_stats")
+            _lib.check(L.c2m_norm_stats_rep(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), N, C, S, mode,
+                                            eps, momentum, rep, dt, _stream()), "norm_stats")
             _lib.check(L.c2m_norm_apply(_p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(gb), None if only else _p(y), _p(yn), N, C, S,
                                         mode, ACT[act], LRELU_SLOPE, dt, _stream()), "norm_apply")
         if only and _NC8_POISON:
@@ -2181,11 +2184,11 @@ class _NormActFn(torch.autograd.Function):
             dx._c2m_nc8 = (dx._version, dxn)
         if ggb is not None and ggb.dtype != ctx.gb_dtype:
             ggb = ggb.to(ctx.gb_dtype)
-        return dx, dgamma, dbeta, ggb, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, ggb, None, None, None, None, None, None, None, None, None
 
 
-def _norm_act(*args):
-    y, yn = _NormActFn.apply(*args)
+def _norm_act(*args, rep=1):
+    y, yn = _NormActFn.apply(*args, rep)
     if yn is not None and _NormActFn.last_only:
         _mark_nc8_only(y, yn)                     # y's NCHW storage was never written
     elif yn is not None:
@@ -2193,10 +2196,12 @@ def _norm_act(*args):
     return y
 
 
-def batch_norm_act(x, gamma, beta, running_mean, running_var, act=None, eps=1e-5, momentum=0.1, feeds=None, private_input=False):
+def batch_norm_act(x, gamma, beta, running_mean, running_var, act=None, eps=1e-5, momentum=0.1, feeds=None, private_input=False, rep=1):
     """private_input: x is a convolution's output that NOTHING else reads (`y = conv(..); y = norm(y)` inside a block) -- where that
-    convolution's backward runs on NC8 kernels, dx is handed back in NC8 form only (no NCHW write, no layout pass)."""
-    return _norm_act(x, gamma, beta, None, running_mean, running_var, 1, act, eps, momentum, feeds, private_input)
+    convolution's backward runs on NC8 kernels, dx is handed back in NC8 form only (no NCHW write, no layout pass).
+    rep: x stands for `rep` identical copies of itself (the generator encodes a source frame once for its T predicted frames); the
+    running variance is updated as the copied batch would have updated it, everything else is the batch's own."""
+    return _norm_act(x, gamma, beta, None, running_mean, running_var, 1, act, eps, momentum, feeds, private_input, rep=rep)
 
 
 def instance_norm_act(x, gamma=None, beta=None, act=None, eps=1e-5, feeds=None, private_input=False):

@@ -260,6 +260,14 @@ int c2m_norm_set_fused(int on);       /* tests / A/B: 0 = always the three-launc
 int c2m_norm_fwd(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
                  const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode, float eps,
                  float momentum, int act, float slope, int dt, void* stream);
+/* The two entries above with a replication count (mode 1 only; rep = 1 is what they call): the batch stands for `rep` identical
+ * copies of itself (one encoded source frame shared by `rep` predicted frames).  mean, invstd and y are the batch's own; only the
+ * running variance sees the larger count: unbiased = m2 * rep / (n * rep - 1), what the statistics of the copied batch would give. */
+int c2m_norm_stats_rep(const void* x, float* mean, float* invstd, float* running_mean, float* running_var,
+                       float* workspace, int N, int C, long S, int mode, float eps, float momentum, int rep, int dt, void* stream);
+int c2m_norm_fwd_rep(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
+                     const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode, float eps,
+                     float momentum, int rep, int act, float slope, int dt, void* stream);
 /* y_nc8 / dx_nc8 (optional; bf16 tensors with S % 8 == 0): the result ALSO in the channel-blocked layout [N][ceil(C/8)][S][8] the
  * NC8 convolutions consume (c2m_nchw_to_nc8's), written by the same pass -- the activation feeds a convolution, the gradient is the
  * dY of the convolution in front.                                                                                              */
