@@ -81,6 +81,26 @@ __device__ __forceinline__ int spatial_off(const int4 tp, int ots, int oys, int 
     return ok ? it * in_st + iy * in_sh + ix : -1;
 }
 
+// Split operand mode of the direct kernels (conv_igemm_kernel, PREC = 2): an fp32 value as the exact sum of
+// three bf16 pieces, v == p0 + p1 + p2 bit for bit, split by TRUNCATION (no piece can overflow; every piece carries v's sign and
+// at most 8 significant bits).  Inf and NaN give a NaN piece (Inf - Inf), so non-finite inputs still reach the output.
+// Returns the pieces as the high halves of three fp32 bit patterns (c2m_pack_hi pairs them into bf16x2 words).
+__device__ __forceinline__ void c2m_split3(float v, unsigned& p0, unsigned& p1, unsigned& p2) {
+    p0 = __builtin_bit_cast(unsigned, v) & 0xFFFF0000u;
+    const float r = v - __builtin_bit_cast(float, p0);                  // exact: <= 16 significant bits
+    p1 = __builtin_bit_cast(unsigned, r) & 0xFFFF0000u;
+    p2 = __builtin_bit_cast(unsigned, r - __builtin_bit_cast(float, p1));   // exact: <= 8 significant bits, low half is zero
+}
+// {hi16(lo), hi16(hi)} as one bf16x2 word (v_perm_b32)
+__device__ __forceinline__ unsigned c2m_pack_hi(unsigned lo, unsigned hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
+
+// The six products of the split mode in descending weight: (piece of A, piece of B).  The first C2M_SPLIT_NHIGH go to the main
+// accumulator, the others to a second one that is added at the end (tools/micro/split_bf16_gemm.hip, form s6/lo4).
+#define C2M_SPLIT_NPROD 6
+#define C2M_SPLIT_NHIGH 2
+__device__ constexpr int C2M_SPLIT_PA[C2M_SPLIT_NPROD] = {0, 0, 1, 0, 1, 2};
+__device__ constexpr int C2M_SPLIT_PB[C2M_SPLIT_NPROD] = {0, 1, 0, 2, 1, 0};
+
 template <class P>
 __device__ __forceinline__ void decompose_pix(int pix, const P& p, int& n, int& ot, int& oy, int& ox) {
     ox = pix % p.Wo; int r = pix / p.Wo;

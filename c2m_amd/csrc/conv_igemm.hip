@@ -22,14 +22,27 @@
 // vector-ALU kernels (conv_thin.hip).  The weight gradient is conv_wgrad.hip, the reflect fold conv_fold.hip, the weight
 // packing conv_pack.hip.
 #include "conv_common.h"
+#include <stdlib.h>
+#include <string.h>
 
-// BF = true: bf16 operands (X is a bf16 tensor in HBM -- the bf16 data path --, weights are rounded to bf16, RNE, while they
+// PREC = 0: fp32 operands on the fp32 MFMA.  PREC = 1 (BF): bf16 operands (X is a bf16 tensor in HBM -- the bf16 data path --, weights are rounded to bf16, RNE, while they
 // are staged into LDS; fp32 accumulation; fp32 or bf16 output, ConvP::yh) on v_mfma_f32_32x32x16_bf16 -- one instruction per 16-deep K-step and 32x32 tile.  LDS
 // image [k half h][row][8 bf16] (16 B per lane, conflict-free ds_read_b128).  The K slot order inside a step is
 // permuted identically for A and B so that each gathering thread's values are contiguous: slot(k) = (k % BROWS) *
 // BPASS + k / BROWS (a sum over k does not care about the order).
-template <int BM, int BN, int WGM, int WGN, int NS, int U, bool BF = false>
-__global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
+//
+// PREC = 2: split operands.  X and the weights are fp32 in HBM and are gathered exactly as in the fp32 form (same K order,
+// table, buffer gather, split-K, class batching and epilogue); each value is split into three bf16 pieces (c2m_split3) when it
+// is stored into LDS -- three images [piece][k half][row][8 bf16] per operand in the bf16 form's slot order -- and a 16-deep
+// K-step of a 32x32 tile is the six products a0b0 a0b1 a1b0 a0b2 a1b1 a2b0 on v_mfma_f32_32x32x16_bf16: 6 x 32 cycles against
+// 8 x 64 on the fp32 pipe.  The dropped products are below 2^-24 of the result.  The four low-order products have
+// an accumulator of their own (s6/lo4 of profiles/split_bf16_numerics.txt), so the 128-row tile holds 128 accumulator registers:
+// its launch bound asks for two waves per SIMD (203 VGPRs, no scratch; unbounded it took 261 and one wave).  LDS: 48 KB (128-row
+// tile), 36 KB (64-row), 54 KB (32-row).
+template <int BM, int BN, int WGM, int WGN, int NS, int U, int PREC = 0>
+__global__ __launch_bounds__(256, (PREC == 2 && BM == 128) ? 2 : 1) void conv_igemm_kernel(const ConvP p) {
+    constexpr bool BF = PREC == 1, SP = PREC == 2, HALF = BF || SP;     // HALF: bf16 LDS images
+    constexpr int NP = SP ? 3 : 1;                                       // pieces per operand
     // U = table K-steps (16 deep each) staged per barrier: U = 2 halves the barriers per MFMA at twice the LDS
     constexpr int BK = 16, CK = BK / NS, BKU = BK * U;
     constexpr int TM = BM / WGM, TN = BN / WGN, MI = TM / 32, NI = TN / 32;
@@ -39,11 +52,11 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
     constexpr int A_F4 = BM * BK / 4;         // float4 loads per K-step (whole block)
     constexpr int APASS = (A_F4 + 255) / 256;
     static_assert(WGM * WGN == 4 && BN >= 64 && CK % BROWS == 0, "tile");
-    static_assert(!BF || BROWS <= 2, "bf16 slot packing is written for BN = 128 / 256");
-    __shared__ float sA[BF ? 1 : 2][BF ? 1 : BKU][BF ? 1 : LDA_S];
-    __shared__ float sB[BF ? 1 : 2][BF ? 1 : BKU][BF ? 1 : LDB_S];
-    __shared__ uint4 hA[BF ? 2 * U * 2 * BM : 1];      // [buf][u][h][row] x 8 bf16
-    __shared__ uint4 hB[BF ? 2 * U * 2 * BN : 1];
+    static_assert(!HALF || BROWS <= 2, "bf16 slot packing is written for BN = 128 / 256");
+    __shared__ float sA[HALF ? 1 : 2][HALF ? 1 : BKU][HALF ? 1 : LDA_S];
+    __shared__ float sB[HALF ? 1 : 2][HALF ? 1 : BKU][HALF ? 1 : LDB_S];
+    __shared__ uint4 hA[HALF ? 2 * U * NP * 2 * BM : 1];      // [buf][u][piece][h][row] x 8 bf16
+    __shared__ uint4 hB[HALF ? 2 * U * NP * 2 * BN : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
@@ -79,6 +92,17 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
         for (int j = 0; j < NI; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // split: the four low-order products accumulate apart and are added once at the end, so the main accumulator is rounded
+    // twice per K-step instead of six times (profiles/split_bf16_numerics.txt: 1.7x less error at K = 16384)
+    f32x16 lo[SP ? MI : 1][SP ? NI : 1];
+    if constexpr (SP) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NI; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) lo[i][j][r] = 0.f;
+    }
 
     float4 ra[U][APASS];
     float rb[BF ? 1 : U][BF ? 1 : BPASS];
@@ -167,6 +191,41 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
                     const int h = BROWS == 1 ? hh : brow0;
                     b8[h * BN + bp] = __builtin_bit_cast(uint4, q);
                 }
+            } else if constexpr (SP) {
+                uint4* __restrict__ a8 = hA + (long)((buf * U + u) * NP * 2) * BM;
+#pragma unroll
+                for (int s = 0; s < APASS; ++s) {
+                    const int r = arow + s * 64;
+                    if (A_F4 >= 256 || r < BM) {
+                        const float4 v = ra[u][s];
+                        unsigned x[3], y[3], z[3], w[3];
+                        c2m_split3(v.x, x[0], x[1], x[2]); c2m_split3(v.y, y[0], y[1], y[2]);
+                        c2m_split3(v.z, z[0], z[1], z[2]); c2m_split3(v.w, w[0], w[1], w[2]);
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) {
+                            unsigned* __restrict__ aq = reinterpret_cast<unsigned*>(a8 + q * 2 * BM);
+                            if constexpr (BROWS == 1) {    // slot = k: 4 consecutive slots in half akq / 8
+                                *reinterpret_cast<uint2*>(aq + ((akq >> 3) * BM + r) * 4 + ((akq & 7) >> 1)) =
+                                    make_uint2(c2m_pack_hi(x[q], y[q]), c2m_pack_hi(z[q], w[q]));
+                            } else {                        // even k -> half 0, odd k -> half 1 (the bf16 form's slots)
+                                aq[(0 * BM + r) * 4 + (akq >> 2)] = c2m_pack_hi(x[q], z[q]);
+                                aq[(1 * BM + r) * 4 + (akq >> 2)] = c2m_pack_hi(y[q], w[q]);
+                            }
+                        }
+                    }
+                }
+                uint4* __restrict__ b8 = hB + (long)((buf * U + u) * NP * 2) * BN;
+#pragma unroll
+                for (int hh = 0; hh < BPASS / 8; ++hh) {
+                    unsigned pc[8][3];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) c2m_split3(rb[u][hh * 8 + e], pc[e][0], pc[e][1], pc[e][2]);
+                    const int h = BROWS == 1 ? hh : brow0;
+#pragma unroll
+                    for (int q = 0; q < 3; ++q)
+                        b8[(q * 2 + h) * BN + bp] = make_uint4(c2m_pack_hi(pc[0][q], pc[1][q]), c2m_pack_hi(pc[2][q], pc[3][q]),
+                                                               c2m_pack_hi(pc[4][q], pc[5][q]), c2m_pack_hi(pc[6][q], pc[7][q]));
+                }
             } else {
 #pragma unroll
                 for (int s = 0; s < APASS; ++s) {
@@ -193,7 +252,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
         const bool more = kt + U < kt_end;
         // interleaved gather issue (below): +9...14 % on the 64-row tile, a few % on the 32-row tile, nothing on the
         // 128-row tile (its 32-MFMA steps already cover the gathers with 3 blocks/CU, and it would pay 8 more VGPRs)
-        constexpr bool IL = !BF && U == 1 && BM < 128;
+        constexpr bool IL = PREC == 0 && U == 1 && BM < 128;
         if (!IL && more) load_tile(kt + U);
         // all fragment reads of a 16-deep step are issued first (own registers each), so the LDS latency of k-pair
         // kk+1.. hides behind the MFMAs of kk (the compiler otherwise recycles 4 VGPRs and serialises read -> mfma)
@@ -212,6 +271,30 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
 #pragma unroll
                     for (int j = 0; j < NI; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        } else if constexpr (SP) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint4* __restrict__ a8 = hA + (long)((cur * U + u) * NP * 2 + (lane >> 5)) * BM;
+                const uint4* __restrict__ b8 = hB + (long)((cur * U + u) * NP * 2 + (lane >> 5)) * BN;
+                bf16x8 a[3][MI], b[3][NI];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+#pragma unroll
+                    for (int i = 0; i < MI; ++i) a[q][i] = __builtin_bit_cast(bf16x8, a8[q * 2 * BM + wm * TM + i * 32 + (lane & 31)]);
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) b[q][j] = __builtin_bit_cast(bf16x8, b8[q * 2 * BN + wn * TN + j * 32 + (lane & 31)]);
+                }
+                // product-major: MI * NI independent accumulators between two MFMAs on the same one
+#pragma unroll
+                for (int q = 0; q < C2M_SPLIT_NPROD; ++q)
+#pragma unroll
+                    for (int i = 0; i < MI; ++i)
+#pragma unroll
+                        for (int j = 0; j < NI; ++j) {
+                            f32x16& d = q < C2M_SPLIT_NHIGH ? acc[i][j] : lo[i][j];
+                            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[C2M_SPLIT_PA[q]][i], b[C2M_SPLIT_PB[q]][j], d, 0, 0, 0);
+                        }
             }
         } else if constexpr (IL) {
             // One scheduling region per K-step: the gathers (and their address arithmetic) of the NEXT step are issued in
@@ -308,6 +391,12 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvP p) {
         cur ^= 1;
     }
 
+    if constexpr (SP) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NI; ++j) acc[i][j] += lo[i][j];
+    }
     // ---- epilogue: acc[i][j][r] -> row m = ..(r&3)+8*(r>>2)+4*(lane>>5), col pix = ..(lane&31)
     const bool direct = p.splits == 1;
     const bool yh = BF && p.yh && direct;                 // bf16 output elements (slabs are fp32)
@@ -423,18 +512,65 @@ __global__ void splitk_reduce_vec_kernel(const float4* __restrict__ slab, T* __r
     }
 }
 
+// C2M_DIRECT_MATH = fp32 | split | auto (default): the matrix instruction of the fp32 launches of conv_igemm_kernel.  Read at
+// every launch, as C2M_FOLD_GENERAL is.  0 fp32, 1 split, 2 auto, -1 anything else (the launch is refused).
+static int direct_math() {
+    const char* e = getenv("C2M_DIRECT_MATH");
+    if (!e || !*e || !strcmp(e, "auto")) return 2;
+    if (!strcmp(e, "fp32")) return 0;
+    if (!strcmp(e, "split")) return 1;
+    return -1;
+}
+
+// Split launches since the last reset, per [tile rows 32, 64, 128][NS 1, 2, 4]: one entry per PREC = 2 instantiation
+constexpr int C2M_DIRECT_COUNTS = 9;
+static long direct_counts[C2M_DIRECT_COUNTS];
+static void direct_count(int tile, int ns) {
+    __atomic_fetch_add(&direct_counts[tile * 3 + (ns == 1 ? 0 : (ns == 2 ? 1 : 2))], 1L, __ATOMIC_RELAXED);
+}
+C2M_API int c2m_direct_math_counts(int64_t* out, int reset) {
+    for (int i = 0; i < C2M_DIRECT_COUNTS; ++i) {
+        const long v = reset ? __atomic_exchange_n(&direct_counts[i], 0L, __ATOMIC_RELAXED) : __atomic_load_n(&direct_counts[i], __ATOMIC_RELAXED);
+        if (out) out[i] = v;
+    }
+    return C2M_DIRECT_COUNTS;
+}
+
+// Does this forward / data-gradient launch run on split operands?  mode: direct_math().
+// auto, from the bench step's launches timed in both modes in one job (profiles/splitbf16_conv_shape_table_{fp32,split}.txt;
+// time of the fp32 launches over the time of the same launches split, summed per group):
+//   128-row tile (M > 64):   K >= 256: 34 shapes, 3.81 -> 2.84 ms, 1.34x (0.95 ... 1.70);  K < 256: 2 shapes, 1.24x
+//   64-row tile (M 33..64):  K >= 256: 10 shapes, 1.61 -> 1.32 ms, 1.23x (0.93 ... 1.44);  K < 256: 3 shapes, 1.01x (0.80, 0.84, 1.06)
+//   32-row tile (M <= 32):   14 shapes, 2.27 -> 2.42 ms, 0.94x (0.87 ... 1.00): 12 MFMAs per wave and K-step against 18 staged
+//                            elements per thread -- the gather and the split, not the matrix pipe, set its time
+static bool igemm_split_pays(int mode, int M, int nk) {
+    if (mode != 2) return mode == 1;
+    return M > 64 || (M > 32 && nk >= 16);
+}
+
+// prec: 0 fp32 MFMA, 1 bf16 operands, 2 split operands (the kernel's PREC)
 template <int BM, int BN, int WGM, int WGN>
-static int launch_igemm(const ConvP& p, int ns, int splits, hipStream_t s, bool bf16) {
+static int launch_igemm(const ConvP& p, int ns, int splits, hipStream_t s, int prec) {
     dim3 grid((unsigned)c2m_cdiv(p.Npix, BN) * c2m_cdiv(p.M, BM) * splits * p.ncls);
     constexpr int U = 1;
-    if (bf16) {
+    if (prec == 1) {
         constexpr int UB = 2;      // bf16: 4 MFMAs per 16-deep step and wave, so two steps per barrier
         switch (ns) {
-            case 1: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 1, UB, true>), grid, dim3(256), 0, s, p); break;
-            case 2: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 2, UB, true>), grid, dim3(256), 0, s, p); break;
-            case 4: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 4, UB, true>), grid, dim3(256), 0, s, p); break;
+            case 1: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 1, UB, 1>), grid, dim3(256), 0, s, p); break;
+            case 2: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 2, UB, 1>), grid, dim3(256), 0, s, p); break;
+            case 4: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 4, UB, 1>), grid, dim3(256), 0, s, p); break;
             default: return (int)hipErrorInvalidValue;
         }
+        return (int)hipGetLastError();
+    }
+    if (prec == 2) {               // split: 6 * MI * NI MFMAs per 16-deep step and wave, one step per barrier
+        switch (ns) {
+            case 1: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 1, U, 2>), grid, dim3(256), 0, s, p); break;
+            case 2: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 2, U, 2>), grid, dim3(256), 0, s, p); break;
+            case 4: hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WGM, WGN, 4, U, 2>), grid, dim3(256), 0, s, p); break;
+            default: return (int)hipErrorInvalidValue;
+        }
+        direct_count(BM == 32 ? 0 : (BM == 64 ? 1 : 2), ns);
         return (int)hipGetLastError();
     }
     switch (ns) {
@@ -557,9 +693,13 @@ C2M_API int c2m_conv_igemm(const float* A, const void* X, void* Y, void* Y_inter
     }
     const bool bf16 = g[C2M_G_PRECISION] == 1;                          // operand precision: 0 fp32 (exact), 1 bf16 (fp32 accumulate)
     if (bf16 ? !p.xh : (p.xh || p.yh)) return (int)hipErrorInvalidValue;   // bf16 kernels gather bf16 X; fp32 kernels are fp32 only
-    if (p.M <= 32)      return launch_igemm<32, 256, 1, 4>(p, ns, splits, s, bf16);
-    else if (p.M <= 64) return launch_igemm<64, 128, 2, 2>(p, ns, splits, s, bf16);
-    else                return launch_igemm<128, 128, 2, 2>(p, ns, splits, s, bf16);
+    // fp32 operands: the exact fp32 MFMA, or the same launch on split-bf16 operands (C2M_DIRECT_MATH)
+    const int math = bf16 ? 0 : direct_math();
+    if (math < 0) return (int)hipErrorInvalidValue;
+    const int prec = bf16 ? 1 : (igemm_split_pays(math, p.M, p.nk) ? 2 : 0);
+    if (p.M <= 32)      return launch_igemm<32, 256, 1, 4>(p, ns, splits, s, prec);
+    else if (p.M <= 64) return launch_igemm<64, 128, 2, 2>(p, ns, splits, s, prec);
+    else                return launch_igemm<128, 128, 2, 2>(p, ns, splits, s, prec);
 }
 
 C2M_API int c2m_splitk_reduce(const float* slab, void* out, const float* bias, long total, int splits,

@@ -224,6 +224,12 @@ int c2m_conv_wino_wgrad3d(const float* dY, const float* X, float* slab, float* d
  * MFMA + one thread per (image, row, corner) for the four targets that receive three ring terms.  Every element of dX has one
  * writer: no atomics, bit-repeatable.  w: native [C][M][3][3] (C = the layer's output channels, M = its input channels);
  * apack: c2m_ring_pack_floats(C, M) floats written by c2m_ring_pack; dY [N][C][H][W]; H, W >= 4; tensors < 2 GiB.            */
+/* Split operand mode of the direct fp32 forward / data-gradient kernel (conv_igemm_kernel; knob C2M_DIRECT_MATH = fp32 | split |
+ * auto, read at every launch): out[9] (may be NULL) = launches that ran on split-bf16 operands since the last reset, indexed
+ * [tile rows: 32, 64, 128][NS: 1, 2, 4] -- one entry per instantiation the launcher can pick; reset != 0 zeroes the counters.
+ * Returns 9.                                                                                                                */
+int c2m_direct_math_counts(int64_t* out, int reset);
+
 long c2m_ring_pack_floats(int C, int M);
 int c2m_ring_pack(const float* w, float* apack, int C, int M, void* stream);
 int c2m_reflect_ring_dgrad(const float* apack, const float* w, const float* dY, float* dX, int N, int C, int M, int H, int W,
