@@ -1,0 +1,316 @@
+// Dense inverse search optical flow (gfx950): a classical, weight-free flow a -> b between two frames, in pixels, channel 0 = x,
+// with a(x) ~ b(x + flow(x)) -- the convention of c2m_occlusion_splat and of FlowNet2's output.  c2m_amd.flow.dense_flow drives
+// it; DESIGN.md 4.2l has the algorithm, operation by operation (tests/dense_flow_np.py restates it in numpy), and the cost.
+//
+//   fl_pyramid_kernel       gray (0.299 R + 0.587 G + 0.114 B of the frame mapped to 0..255) and every 2x2-mean level of both frames
+//                           of all N pairs in ONE launch: a workgroup owns a 64 x 64 tile of level 0, keeps every level of it in
+//                           LDS and halves it level by level.  A tile origin is a multiple of 64 >> l at level l, and the 2 x 2
+//                           block of a level-(l+1) pixel, clamped to the last row and column, lies in the same tile: no workgroup
+//                           reads what another one wrote.
+//   fl_patch_search_kernel  one wave per 8 x 8 patch (stride 4; a last, more overlapping patch where the size is no multiple of 4),
+//                           lane = (py, px) = (lane >> 3, lane & 7).  The lane's template pixel and its two gradients stay in
+//                           registers; every sum over the patch is a wave_sum_all (fixed shuffle order, so bit-repeatable).  A fixed
+//                           number of inverse-compositional steps, no early exit: the result cannot depend on which waves finished
+//                           first.  The x2 up-sampling of the coarser level's flow is fused into the read of the initial flow.
+//                           One record per patch: u, v, mean(J) - mean(T) at the final flow.
+//   fl_densify_kernel       one thread per pixel: the <= 3 x 3 patches that cover it in ascending (oy, ox) order, each weighted by
+//                           1 / max(1, |residual of that patch at this pixel|).  No atomics.  With shift > 0 it writes the flow of a
+//                           coarser level straight at the size of level 0 (2^shift * f[y >> shift][x >> shift]).
+//
+// The window of b that a patch samples is read through L1 / L2, not staged in LDS: a level image of the training
+// size is <= 128 KB, a patch touches about 9 x 9 floats of it per step, and with no early exit the flow is bounded only at the
+// END of the search (step 6), so a staged 25 x 25 window would still need the global path next to it.
+#include "common.h"
+#include "dtype.h"
+
+#define C2M_FLOW_MAX_LEVELS 7           // 64 >> 6 = 1: the coarsest level a 64 x 64 tile still holds a pixel of
+#define C2M_FLOW_MAX_SIDE 32768
+#define C2M_FLOW_PATCH 8
+#define C2M_FLOW_STRIDE 4
+#define C2M_FLOW_MAX_ITERS 1024
+#define C2M_FLOW_DET_MIN 40.96f         // 1e-2 * 64^2
+#define C2M_FLOW_MAX_STEP2 64.0f        // (8 px)^2
+
+// ------------------------------------------------------------------------------------------------ sizes and the workspace
+// floats: per level l the images a[N][h][w] then b[N][h][w]; then the patch records of the largest level [N][npy][npx][3]; then
+// the dense flows of the levels 1 .. levels - 1, [N][2][h][w] each (level 0's goes to the caller's tensor).
+struct FlLayout {
+    int h[C2M_FLOW_MAX_LEVELS], w[C2M_FLOW_MAX_LEVELS];
+    long img[C2M_FLOW_MAX_LEVELS], flow[C2M_FLOW_MAX_LEVELS], rec, total;
+};
+
+static inline int fl_patches(int n) {                       // origins 0, 4, 8, ... <= n - 8, plus n - 8 if that is not one of them
+    return (n - C2M_FLOW_PATCH) / C2M_FLOW_STRIDE + 1 + ((n - C2M_FLOW_PATCH) % C2M_FLOW_STRIDE != 0);
+}
+
+static inline bool fl_level_ok(long N, long h, long w) {
+    return N >= 0 && N < (1L << 24) && h >= C2M_FLOW_PATCH && w >= C2M_FLOW_PATCH && h <= C2M_FLOW_MAX_SIDE && w <= C2M_FLOW_MAX_SIDE;
+}
+
+static bool fl_layout(long N, long H, long W, int levels, FlLayout& L) {
+    if (levels < 1 || levels > C2M_FLOW_MAX_LEVELS || !fl_level_ok(N, H, W)) return false;
+    long off = 0, h = H, w = W;
+    for (int l = 0; l < levels; ++l, h = (h + 1) / 2, w = (w + 1) / 2) {
+        if (h < C2M_FLOW_PATCH || w < C2M_FLOW_PATCH) return false;
+        L.h[l] = (int)h; L.w[l] = (int)w; L.img[l] = off;
+        off += 2 * N * h * w;
+    }
+    L.rec = off;
+    off += N * fl_patches((int)H) * fl_patches((int)W) * 3;
+    L.flow[0] = -1;
+    for (int l = 1; l < levels; ++l) { L.flow[l] = off; off += 2 * N * L.h[l] * (long)L.w[l]; }
+    L.total = off;
+    return true;
+}
+
+C2M_API long c2m_flow_workspace_bytes(int N, int H, int W, int levels) {
+    FlLayout L;
+    return fl_layout(N, H, W, levels, L) ? L.total * 4 : -1;
+}
+
+C2M_API long c2m_flow_workspace_offset(int N, int H, int W, int levels, int what, int level) {
+    FlLayout L;
+    if (!fl_layout(N, H, W, levels, L) || level < 0 || level >= levels) return -1;
+    switch (what) {
+        case 0: return L.img[level];
+        case 1: return L.img[level] + (long)N * L.h[level] * L.w[level];
+        case 2: return L.flow[level];
+        case 3: return L.rec;
+        default: return -1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ pyramid
+struct FlPyrP {
+    const void* src[2]; float* ws;
+    int N, H, W, levels, ty, tx;
+    int h[C2M_FLOW_MAX_LEVELS], w[C2M_FLOW_MAX_LEVELS];
+    long img[C2M_FLOW_MAX_LEVELS];
+    float lo, scale;
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void fl_pyramid_kernel(const FlPyrP p) {
+    __shared__ float lds[4096 + 1024 + 256 + 64 + 16 + 4 + 1];
+    const int tiles = p.ty * p.tx, tid = threadIdx.x;
+    const long items = 2L * p.N * tiles;
+    for (long item = blockIdx.x; item < items; item += gridDim.x) {             // workgroup-uniform
+        const int tile = (int)(item % tiles), ty = tile / p.tx, tx = tile % p.tx;
+        const long im = item / tiles;                                           // a of pair 0 .. N-1, then b of pair 0 .. N-1
+        const int which = im >= p.N;
+        const T* __restrict__ src = (const T*)p.src[which] + (im - (long)which * p.N) * 3 * p.H * (long)p.W;
+        const long plane = (long)p.H * p.W;
+        __syncthreads();                                                        // the previous item's last level has been read
+        for (int k = 0; k < 16; ++k) {
+            const int idx = k * 256 + tid, gy = ty * 64 + (idx >> 6), gx = tx * 64 + (idx & 63);
+            if (gy < p.H && gx < p.W) {
+                const long q = (long)gy * p.W + gx;
+                const float r = (c2m_ld(src, q) - p.lo) * p.scale, g = (c2m_ld(src, plane + q) - p.lo) * p.scale,
+                            b = (c2m_ld(src, 2 * plane + q) - p.lo) * p.scale;
+                const float v = (0.299f * r + 0.587f * g) + 0.114f * b;
+                lds[idx] = v;
+                p.ws[p.img[0] + im * plane + q] = v;
+            }
+        }
+        int below = 0;                                                          // LDS offset of level l - 1
+        for (int l = 1; l < p.levels; ++l) {                                    // workgroup-uniform
+            __syncthreads();
+            const int side = 64 >> l, here = below + (4096 >> (2 * (l - 1)));
+            const int h = p.h[l], w = p.w[l], hb = p.h[l - 1], wb = p.w[l - 1];
+            for (int idx = tid; idx < side * side; idx += 256) {
+                const int ly = idx >> (6 - l), lx = idx & (side - 1), gy = ty * side + ly, gx = tx * side + lx;
+                if (gy < h && gx < w) {
+                    // rows 2 gy, min(2 gy + 1, hb - 1) of the level below, as rows of this tile (origin 2 * side * ty)
+                    const int y0 = 2 * ly, y1 = min(2 * gy + 1, hb - 1) - 2 * side * ty;
+                    const int x0 = 2 * lx, x1 = min(2 * gx + 1, wb - 1) - 2 * side * tx;
+                    const float* b = lds + below;
+                    const int s = 2 * side;
+                    const float v = (((b[y0 * s + x0] + b[y0 * s + x1]) + b[y1 * s + x0]) + b[y1 * s + x1]) * 0.25f;
+                    lds[here + idx] = v;
+                    p.ws[p.img[l] + im * ((long)h * w) + (long)gy * w + gx] = v;
+                }
+            }
+            below = here;
+        }
+    }
+}
+
+C2M_API int c2m_flow_pyramid(const void* a, const void* b, int dt, float lo, float hi, int N, int H, int W, int levels,
+                             void* workspace, long workspace_bytes, void* stream) {
+    C2M_ENTER();
+    FlLayout L;
+    if (!fl_layout(N, H, W, levels, L) || (dt != C2M_F32 && dt != C2M_BF16) || !(hi > lo) || !(hi - lo < 3.0e38f))
+        return (int)hipErrorInvalidValue;
+    if (N == 0) return 0;
+    if (!a || !b || !workspace || workspace_bytes < L.total * 4 || !c2m_aligned(4, workspace) ||
+        !c2m_aligned(dt == C2M_BF16 ? 2 : 4, a, b))
+        return (int)hipErrorInvalidValue;
+    FlPyrP p;
+    p.src[0] = a; p.src[1] = b; p.ws = (float*)workspace;
+    p.N = N; p.H = H; p.W = W; p.levels = levels; p.ty = (H + 63) / 64; p.tx = (W + 63) / 64;
+    for (int l = 0; l < C2M_FLOW_MAX_LEVELS; ++l) {
+        p.h[l] = l < levels ? L.h[l] : 0; p.w[l] = l < levels ? L.w[l] : 0; p.img[l] = l < levels ? L.img[l] : 0;
+    }
+    p.lo = lo; p.scale = (float)(255.0 / ((double)hi - (double)lo));
+    const long items = 2L * N * p.ty * p.tx;
+    const dim3 grid((unsigned)(items < 65536 ? items : 65536));
+    C2M_DISPATCH_DT(dt, hipLaunchKernelGGL(fl_pyramid_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, p););
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ bilinear sample of b's level
+// The coordinate is clamped to the image FIRST, so 0 <= x0 <= x1 <= w - 1 and 0 <= y0 <= y1 <= h - 1 whatever the flow is (a NaN
+// goes to 0: fmaxf returns its other operand): every address of the gather is inside the level image.  The bound of step 6 on
+// a KEPT flow (|u - u0| <= 8) says how far from the patch the final samples lie (a 25 x 25 window); it is not what keeps the
+// reads in bounds, the clamp is.
+__device__ __forceinline__ float fl_sample(const float* __restrict__ img, int h, int w, float fx, float fy) {
+    fx = fminf(fmaxf(fx, 0.f), (float)(w - 1));
+    fy = fminf(fmaxf(fy, 0.f), (float)(h - 1));
+    const float x0f = floorf(fx), y0f = floorf(fy);
+    const int x0 = (int)x0f, y0 = (int)y0f, x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const float ax = fx - x0f, ay = fy - y0f;
+    const float* __restrict__ r0 = img + (long)y0 * w;
+    const float* __restrict__ r1 = img + (long)y1 * w;
+    const float top = r0[x0] * (1.f - ax) + r0[x1] * ax;
+    const float bot = r1[x0] * (1.f - ax) + r1[x1] * ax;
+    return top * (1.f - ay) + bot * ay;
+}
+
+// ------------------------------------------------------------------------------------------------ patch search
+struct FlPsP {
+    const float* ia; const float* ib; const float* init; float* rec;
+    int h, w, npy, npx, hc, wc, shift, iters;
+    long waves;                                                                 // N * npy * npx: one wave each
+};
+
+__global__ __launch_bounds__(256) void fl_patch_search_kernel(const FlPsP p) {
+    const int lane = threadIdx.x & 63, py = lane >> 3, px = lane & 7;
+    const int h = p.h, w = p.w;
+    const long nwaves = (long)gridDim.x * 4;
+    for (long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6); i < p.waves; i += nwaves) {          // wave-uniform
+        const int jx = (int)(i % p.npx);
+        const long t = i / p.npx;
+        const int jy = (int)(t % p.npy);
+        const long n = t / p.npy;
+        const int ox = min(C2M_FLOW_STRIDE * jx, w - C2M_FLOW_PATCH), oy = min(C2M_FLOW_STRIDE * jy, h - C2M_FLOW_PATCH);
+        const int x = ox + px, y = oy + py;                                     // inside the image: ox + 7 <= w - 1
+        const float* __restrict__ A = p.ia + n * ((long)h * w);
+        const float* __restrict__ B = p.ib + n * ((long)h * w);
+        const float* __restrict__ row = A + (long)y * w;
+        const float T = row[x];
+        const float gx = 0.5f * (row[min(x + 1, w - 1)] - row[max(x - 1, 0)]);
+        const float gy = 0.5f * (A[(long)min(y + 1, h - 1) * w + x] - A[(long)max(y - 1, 0) * w + x]);
+        float u0 = 0.f, v0 = 0.f;
+        if (p.init) {                                                           // 2 * f_coarser[y // 2][x // 2] at the patch centre
+            const int cy = (oy + 3) >> p.shift, cx = (ox + 3) >> p.shift;      // < hc, wc = ceil(h, w / 2^shift)
+            const float* __restrict__ F = p.init + n * 2 * ((long)p.hc * p.wc) + (long)cy * p.wc + cx;
+            const float s = (float)(1 << p.shift);
+            u0 = s * F[0];
+            v0 = s * F[(long)p.hc * p.wc];
+        }
+        const float mT = wave_sum_all(T) * 0.015625f, Tm = T - mT;
+        const float a = wave_sum_all(gx * gx), b = wave_sum_all(gx * gy), c = wave_sum_all(gy * gy);
+        const float det = a * c - b * b;
+        float u = u0, v = v0;
+        if (det > C2M_FLOW_DET_MIN) {                                           // wave-uniform: every lane holds lane 0's sums
+            for (int it = 0; it < p.iters; ++it) {
+                const float J = fl_sample(B, h, w, (float)x + u, (float)y + v);
+                const float mJ = wave_sum_all(J) * 0.015625f;
+                const float r = (J - mJ) - Tm;
+                const float bx = wave_sum_all(r * gx), by = wave_sum_all(r * gy);
+                u -= (c * bx - b * by) / det;
+                v -= (a * by - b * bx) / det;
+            }
+            const float du = u - u0, dv = v - v0;
+            if (!(du * du + dv * dv <= C2M_FLOW_MAX_STEP2)) { u = u0; v = v0; } // further than 8 px (or NaN): back to the initial flow
+        }
+        const float J = fl_sample(B, h, w, (float)x + u, (float)y + v);
+        const float mJ = wave_sum_all(J) * 0.015625f;
+        if (lane == 0) {
+            float* __restrict__ o = p.rec + i * 3;
+            o[0] = u; o[1] = v; o[2] = mJ - mT;
+        }
+    }
+}
+
+C2M_API int c2m_flow_patch_search(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
+                                  int init_shift, float* records, long record_elems, int N, int h, int w, int iters, void* stream) {
+    C2M_ENTER();
+    if (!fl_level_ok(N, h, w) || iters < 0 || iters > C2M_FLOW_MAX_ITERS || init_shift < 0 || init_shift > 1)
+        return (int)hipErrorInvalidValue;
+    if (N == 0) return 0;
+    FlPsP p;
+    p.ia = ia; p.ib = ib; p.init = init; p.rec = records;
+    p.h = h; p.w = w; p.npy = fl_patches(h); p.npx = fl_patches(w);
+    p.hc = (h + (1 << init_shift) - 1) >> init_shift; p.wc = (w + (1 << init_shift) - 1) >> init_shift;
+    p.shift = init_shift; p.iters = iters;
+    p.waves = (long)N * p.npy * p.npx;
+    if (!ia || !ib || !records || image_elems < (long)N * h * w || record_elems < p.waves * 3 ||
+        (init && init_elems < 2L * N * p.hc * p.wc) || !c2m_aligned(4, ia, ib, init, records))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(fl_patch_search_kernel, dim3(c2m_grid(p.waves * 64, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ densify
+struct FlDnP {
+    const float* ia; const float* ib; const float* rec; float* out;
+    int h, w, npy, npx, shift, Ho, Wo;
+    float scale;
+    long total;                                                                 // N * Ho * Wo
+};
+
+__global__ __launch_bounds__(256) void fl_densify_kernel(const FlDnP p) {
+    const int h = p.h, w = p.w;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < p.total; i += (long)gridDim.x * blockDim.x) {
+        const int X = (int)(i % p.Wo);
+        const long t = i / p.Wo;
+        const int Y = (int)(t % p.Ho);
+        const long n = t / p.Ho;
+        const int x = X >> p.shift, y = Y >> p.shift;                           // < w, h: checked by the launcher
+        const float* __restrict__ A = p.ia + n * ((long)h * w);
+        const float* __restrict__ B = p.ib + n * ((long)h * w);
+        const float* __restrict__ R = p.rec + n * 3 * ((long)p.npy * p.npx);
+        const float T = A[(long)y * w + x];
+        // a patch of index j has its origin at min(4 j, n - 8): the indices whose 8 pixels can hold y are ceil((y - 7) / 4) ..
+        // y / 4 + 1 (the last, clamped, patch); the test against the origin picks the <= 3 that do
+        const int jy0 = y < 4 ? 0 : (y - 4) >> 2, jy1 = min((y >> 2) + 1, p.npy - 1);
+        const int jx0 = x < 4 ? 0 : (x - 4) >> 2, jx1 = min((x >> 2) + 1, p.npx - 1);
+        float su = 0.f, sv = 0.f, sw = 0.f;
+        for (int jy = jy0; jy <= jy1; ++jy) {                                   // ascending (oy, ox): the order of the sum is fixed
+            const int oy = min(C2M_FLOW_STRIDE * jy, h - C2M_FLOW_PATCH);
+            if (y < oy || y > oy + C2M_FLOW_PATCH - 1) continue;
+            for (int jx = jx0; jx <= jx1; ++jx) {
+                const int ox = min(C2M_FLOW_STRIDE * jx, w - C2M_FLOW_PATCH);
+                if (x < ox || x > ox + C2M_FLOW_PATCH - 1) continue;
+                const float* __restrict__ q = R + 3 * ((long)jy * p.npx + jx);
+                const float u = q[0], v = q[1], d = q[2];
+                const float r = (fl_sample(B, h, w, (float)x + u, (float)y + v) - T) - d;
+                const float wgt = 1.f / fmaxf(1.f, fabsf(r));
+                su += wgt * u; sv += wgt * v; sw += wgt;
+            }
+        }
+        float* __restrict__ o = p.out + n * 2 * ((long)p.Ho * p.Wo) + (long)Y * p.Wo + X;
+        o[0] = p.scale * (su / sw);                                             // sw > 0: every pixel is covered (h, w >= 8)
+        o[(long)p.Ho * p.Wo] = p.scale * (sv / sw);
+    }
+}
+
+C2M_API int c2m_flow_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
+                             float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, void* stream) {
+    C2M_ENTER();
+    if (!fl_level_ok(N, h, w) || shift < 0 || shift >= C2M_FLOW_MAX_LEVELS || Ho < 1 || Wo < 1 || Ho > C2M_FLOW_MAX_SIDE ||
+        Wo > C2M_FLOW_MAX_SIDE || ((Ho - 1) >> shift) >= h || ((Wo - 1) >> shift) >= w)
+        return (int)hipErrorInvalidValue;
+    if (N == 0) return 0;
+    FlDnP p;
+    p.ia = ia; p.ib = ib; p.rec = records; p.out = flow;
+    p.h = h; p.w = w; p.npy = fl_patches(h); p.npx = fl_patches(w); p.shift = shift; p.Ho = Ho; p.Wo = Wo;
+    p.scale = (float)(1 << shift);
+    p.total = (long)N * Ho * Wo;
+    if (!ia || !ib || !records || !flow || image_elems < (long)N * h * w || record_elems < 3L * N * p.npy * p.npx ||
+        flow_elems < 2 * p.total || !c2m_aligned(4, ia, ib, records, flow))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(fl_densify_kernel, dim3(c2m_grid(p.total, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}

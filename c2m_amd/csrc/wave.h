@@ -15,6 +15,10 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// The same sum, in the same shuffle order and so with the same bits, broadcast to every lane.
+template <class T>
+__device__ __forceinline__ T wave_sum_all(T v) { return __shfl(wave_sum(v), 0, 64); }
+
 // Block-wide sum for blockDim.x == 256 (4 waves), smem >= 4 values.  Result valid in every thread.
 template <class T>
 __device__ __forceinline__ T block_sum_256(T v, T* smem) {

@@ -1,0 +1,187 @@
+"""Optical flow without a checkpoint: dense inverse search on the GPU (csrc/dense_flow.hip).
+
+`dense_flow(a, b)` is the flow a -> b in pixels, channel 0 = x, with a(x) ~ b(x + flow(x)): the convention of
+`ops.occlusion_splat`, of FlowNet2's output and of `train.compute_flow`, whose `target_bw_of` is the flow of (target frame ->
+last input frame) and is read by `ops.label_warp` and `tracking.track_instances` as "pixel p came from p + flow(p)".
+`ClassicFlow` has the call surface of `modules.third_party.flow_net.FlowNet` (4-, 5- and 6-D inputs, `compute_flow_and_conf`), so
+it drops into `train.compute_flow`, into `tracking.tracked_batch`'s inputs and into `interactive.rollout(flow_fn=...)`.
+
+The algorithm is a coarse-to-fine inverse search over 8 x 8 patches at stride 4 (one wave64 per patch), a fixed number of steps
+per patch and a weighted average of the patches that cover a pixel.  There is NO variational refinement, and a motion of more
+than about 8 px at the coarsest level (25 px at 128 x 256, four levels) is out of range.  Nothing here has weights; nothing is
+differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
+"""
+import torch
+import torch.nn as nn
+
+from . import _lib, ops
+
+PATCH, STRIDE, MAX_LEVELS = 8, 4, 7
+
+
+def pyramid_sizes(H, W, levels=None):
+    """[(h, w)] of every level: level l + 1 is ((h + 1) // 2, (w + 1) // 2), added while min(h, w) // 2 >= 16, at most
+    `levels` (and at most 7, what the pyramid kernel's tile holds)."""
+    if levels is not None and int(levels) < 1:
+        raise ValueError(f"levels must be >= 1, got {levels}")
+    sizes = [(int(H), int(W))]
+    cap = MAX_LEVELS if levels is None else min(int(levels), MAX_LEVELS)
+    while len(sizes) < cap and min(sizes[-1]) // 2 >= 16:
+        h, w = sizes[-1]
+        sizes.append(((h + 1) // 2, (w + 1) // 2))
+    return sizes
+
+
+def patch_origins(n):
+    """Patch origins along an axis of n >= 8 pixels: 0, 4, 8, ... <= n - 8, plus n - 8 if that is not one of them."""
+    if n < PATCH:
+        raise ValueError(f"an axis of {n} pixels holds no {PATCH}-pixel patch")
+    o = list(range(0, n - PATCH + 1, STRIDE))
+    return o if o[-1] == n - PATCH else o + [n - PATCH]
+
+
+def _pair(a, b):
+    """The checks of an image pair, before the device is looked at: (N, H, W)."""
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError(f"{name} must be a [N,3,H,W] tensor, got {list(getattr(t, 'shape', ()))}")
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{name} must be fp32 or bf16, got {t.dtype}")
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError(f"a and b must have one shape and dtype, got {list(a.shape)} {a.dtype} and {list(b.shape)} {b.dtype}")
+    N, _, H, W = a.shape
+    if H < PATCH or W < PATCH:
+        raise ValueError(f"dense_flow needs H, W >= {PATCH}, got {H} x {W}")
+    if not (a.is_cuda and b.is_cuda):
+        raise ValueError("dense_flow needs tensors on a HIP device (no CPU fallback by design)")
+    ops._on_current_device(a, b)
+    return N, H, W
+
+
+def _level_images(ia, ib):
+    if not all(isinstance(t, torch.Tensor) and t.dim() == 3 and t.dtype == torch.float32 for t in (ia, ib)) or ia.shape != ib.shape:
+        raise ValueError("level images must be two fp32 [N,h,w] tensors of one shape")
+    if ia.shape[1] < PATCH or ia.shape[2] < PATCH:
+        raise ValueError(f"a level needs h, w >= {PATCH}, got {ia.shape[1]} x {ia.shape[2]}")
+    ops._hip_only(ia, ib)
+    ops._on_current_device(ia, ib)
+    return ia.detach().contiguous(), ib.detach().contiguous()
+
+
+def flow_pyramid(a, b, value_range=(0, 1), levels=None):
+    """Gray pyramids of both frames of N pairs in one launch -> (workspace, sizes, images): `workspace` is the fp32 buffer of
+    one dense_flow call (c2m_flow_workspace_bytes), sizes = pyramid_sizes, images[l] = (a_l, b_l), [N,h,w] views of it."""
+    N, H, W = _pair(a, b)
+    lo, hi = (float(v) for v in value_range)
+    if not hi > lo:
+        raise ValueError(f"value_range must be (lo, hi) with lo < hi, got {value_range}")
+    sizes = pyramid_sizes(H, W, levels)
+    L, n = _lib.lib(), len(sizes)
+    nbytes = L.c2m_flow_workspace_bytes(N, H, W, n)
+    if nbytes < 0:
+        raise ValueError(f"dense_flow: sizes out of range (N={N}, H={H}, W={W}, levels={n})")
+    work = torch.empty(nbytes // 4, device=a.device, dtype=torch.float32)
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    _lib.check(L.c2m_flow_pyramid(ops._p(a), ops._p(b), int(a.dtype == torch.bfloat16), lo, hi, N, H, W, n, ops._p(work), nbytes,
+                                  ops._stream()), "flow_pyramid")
+    images = []
+    for l, (h, w) in enumerate(sizes):
+        o = L.c2m_flow_workspace_offset(N, H, W, n, 0, l)
+        images.append((work[o:o + N * h * w].view(N, h, w), work[o + N * h * w:o + 2 * N * h * w].view(N, h, w)))
+    return work, sizes, images
+
+
+def patch_search(ia, ib, init=None, iters=12, out=None):
+    """Steps 1-6 for one level: ia, ib [N,h,w] fp32 -> records [N,npy,npx,3] = (u, v, mean(J) - mean(T)) per patch.  init: None
+    (zero flow), the dense flow [N,2,h,w] of this level, or that of the coarser level [N,2,(h+1)//2,(w+1)//2], which is read as
+    2 * init[y // 2, x // 2]."""
+    ia, ib = _level_images(ia, ib)
+    N, h, w = ia.shape
+    shift = 0
+    if init is not None:
+        coarse = (N, 2, (h + 1) // 2, (w + 1) // 2)
+        if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or tuple(init.shape) not in ((N, 2, h, w), coarse):
+            raise ValueError(f"init must be fp32 {[N, 2, h, w]} or {list(coarse)}, got {list(getattr(init, 'shape', ()))}")
+        ops._hip_only(init)
+        shift = int(tuple(init.shape) != (N, 2, h, w))
+        init = init.detach().contiguous()
+    npy, npx = len(patch_origins(h)), len(patch_origins(w))
+    rec = torch.empty(N, npy, npx, 3, device=ia.device, dtype=torch.float32) if out is None else out
+    _lib.check(_lib.lib().c2m_flow_patch_search(ops._p(ia), ops._p(ib), ia.numel(), ops._p(init), 0 if init is None else init.numel(),
+                                                shift, ops._p(rec), rec.numel(), N, h, w, int(iters), ops._stream()),
+               "flow_patch_search")
+    return rec
+
+
+def densify(ia, ib, records, shift=0, out_size=None, out=None):
+    """Step 7 for one level: the dense flow [N,2,h,w] from the patch records [N,npy,npx,3].  shift, out_size: write
+    2**shift * flow[y >> shift, x >> shift] at out_size = (Ho, Wo) instead (a coarser level brought to level 0)."""
+    ia, ib = _level_images(ia, ib)
+    N, h, w = ia.shape
+    npy, npx = len(patch_origins(h)), len(patch_origins(w))
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.float32 or tuple(records.shape) != (N, npy, npx, 3):
+        raise ValueError(f"records must be fp32 {[N, npy, npx, 3]}, got {list(getattr(records, 'shape', ()))}")
+    ops._hip_only(records)
+    records = records.detach().contiguous()
+    Ho, Wo = (h, w) if out_size is None else (int(v) for v in out_size)
+    flow = torch.empty(N, 2, Ho, Wo, device=ia.device, dtype=torch.float32) if out is None else out
+    _lib.check(_lib.lib().c2m_flow_densify(ops._p(ia), ops._p(ib), ia.numel(), ops._p(records), records.numel(), ops._p(flow),
+                                           flow.numel(), N, h, w, int(shift), Ho, Wo, ops._stream()), "flow_densify")
+    return flow
+
+
+def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12):
+    """Flow a -> b of N image pairs -> [N,2,H,W] fp32 pixels (channel 0 = x; a(x) ~ b(x + flow(x))).
+
+    a, b [N,3,H,W] fp32 or bf16 on the device, H, W >= 8, values in value_range = (lo, hi).  levels: at most that many pyramid
+    levels (by default levels are added while min(h, w) // 2 >= 16).  finest: the last level searched; its flow is brought to
+    level 0 by 2 * f[y // 2, x // 2] per level.  iters: search steps per patch and level, the same for every patch.
+    1 + 2 * (levels - finest) launches on the current stream whatever N is, no synchronisation, no copy to the host; the result
+    is bit-repeatable and that of a pair does not depend on the other pairs of the call.  No gradient flows through it."""
+    with torch.no_grad():
+        work, sizes, images = flow_pyramid(a, b, value_range, levels)
+        N, (H, W), n = a.shape[0], sizes[0], len(sizes)
+        finest, iters = int(finest), int(iters)
+        if not 0 <= finest < n:
+            raise ValueError(f"finest must be a level of the pyramid (0 .. {n - 1}), got {finest}")
+        if not 0 <= iters <= 1024:
+            raise ValueError(f"iters must be 0 .. 1024, got {iters}")
+        L = _lib.lib()
+        rec0 = L.c2m_flow_workspace_offset(N, H, W, n, 3, 0)
+        out = torch.empty(N, 2, H, W, device=a.device, dtype=torch.float32)
+        flow = None
+        for l in range(n - 1, finest - 1, -1):
+            (h, w), (ia, ib) = sizes[l], images[l]
+            npy, npx = len(patch_origins(h)), len(patch_origins(w))
+            rec = patch_search(ia, ib, flow, iters, out=work[rec0:rec0 + N * npy * npx * 3].view(N, npy, npx, 3))
+            if l == finest:
+                return densify(ia, ib, rec, shift=l, out_size=(H, W), out=out)
+            o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)
+            flow = densify(ia, ib, rec, out=work[o:o + 2 * N * h * w].view(N, 2, h, w))
+
+
+class ClassicFlow(nn.Module):
+    """dense_flow behind FlowNet's call surface: `flow, conf = ClassicFlow()(A, B)` for 4-D [N,3,H,W], 5-D [b,n,3,H,W] and 6-D
+    [b,t,n,3,H,W] inputs, with conf = ops.occlusion_splat(flow)[0] as FlowNet computes it.  value_range defaults to (-1, 1),
+    where train.compute_flow puts the frames; ClassicFlow(value_range=(0, 1)).compute_flow_and_conf is the `flow_fn` of
+    interactive.rollout.  No weights, no resize to multiples of 64: any size >= 8."""
+
+    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12):
+        super().__init__()
+        self.value_range, self.levels, self.finest, self.iters = tuple(value_range), levels, finest, iters
+
+    def forward(self, input_A, input_B):
+        size = input_A.size()
+        if len(size) not in (4, 5, 6):
+            raise ValueError(f"ClassicFlow takes [N,3,H,W], [b,n,3,H,W] or [b,t,n,3,H,W], got {list(size)}")
+        if len(size) == 4:
+            return self.compute_flow_and_conf(input_A, input_B)
+        c, h, w = size[-3:]
+        flow, conf = self.compute_flow_and_conf(input_A.contiguous().view(-1, c, h, w), input_B.contiguous().view(-1, c, h, w))
+        return flow.view(*size[:-3], 2, h, w), conf.view(*size[:-3], 1, h, w)
+
+    def compute_flow_and_conf(self, im1, im2):
+        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters)
+        with torch.no_grad():
+            conf = ops.occlusion_splat(flow)[0]
+        return flow, conf

@@ -383,6 +383,35 @@ int c2m_nearest_fill(const uint8_t* hole, const uint8_t* seed, float* planes_f, 
                      int32_t* planes_i, long isb, long isc, long ist, int Ci, int B, int T, int H, int W, int32_t* unfilled,
                      void* workspace, long workspace_bytes, void* stream);
 
+/* ---- dense inverse search optical flow (dense_flow.hip): c2m_amd.flow.dense_flow, ClassicFlow -----------------------------
+ * The reference has no counterpart: its only flow producer is FlowNet2 (modules/third_party/flow_net/flow_net.py), which needs
+ * a checkpoint.  The flow is that of a -> b in pixels, channel 0 = x, a(x) ~ b(x + flow(x)); DESIGN.md 4.2l states every step.
+ * Sizes: 8 <= H, W <= 32768, 1 <= levels <= 7, level l + 1 is ((h + 1) / 2, (w + 1) / 2) and every level is >= 8 on both sides;
+ * a level has (n - 8) / 4 + 1 patches per axis, one more where n - 8 is no multiple of 4 (origin of patch j: min(4 j, n - 8)).
+ * c2m_flow_workspace_bytes: the workspace of one call (-1 for sizes out of range), 4-byte aligned, never zeroed: per level the gray
+ *   images a [N][h][w] then b [N][h][w]; the patch records of level 0 [N][npy][npx][3] (reused by the smaller levels); the flows
+ *   of the levels >= 1, [N][2][h][w].  c2m_flow_workspace_offset: where `what` of `level` starts, in floats (0 image a, 1 image b,
+ *   2 flow, level >= 1; 3 records) or -1.
+ * c2m_flow_pyramid: a, b [N][3][H][W] (dt 0 fp32, 1 bf16) -> every level of both, ONE launch.  A value v becomes
+ *   (v - lo) * (255 / (hi - lo)); gray = (0.299 R + 0.587 G) + 0.114 B; a coarser pixel is (((p00 + p01) + p10) + p11) * 0.25 of
+ *   the 2 x 2 block at (2y, 2x), rows and columns clamped to the last.
+ * c2m_flow_patch_search: ia, ib [N][h][w] (image_elems floats each) -> records [N][npy][npx][3] = (u, v, mean(J) - mean(T)), ONE
+ *   launch, one wave per patch.  init: NULL (zero flow) or the dense flow [N][2][hc][wc] with hc, wc = ceil(h, w / 2^init_shift),
+ *   init_shift 0 or 1, read as 2^init_shift * init[(oy + 3) >> init_shift][(ox + 3) >> init_shift].  iters (<= 1024) steps for
+ *   every patch whose det > 40.96, no early exit; a patch that ends more than 8 px from its initial flow returns to it.
+ * c2m_flow_densify: flow [N][2][Ho][Wo], pixel (Y, X) = 2^shift * the weighted mean at level pixel (Y >> shift, X >> shift) over
+ *   the <= 3 x 3 patches that cover it, ascending (oy, ox), weight 1 / max(1, |(J - T) - record[2]|); ((Ho - 1) >> shift) < h.
+ * Every size and extent is checked before the launch; all three run on `stream`; no atomics, no synchronisation, no host copy:
+ * bit-repeatable, and the result of a pair does not depend on N.                                                               */
+long c2m_flow_workspace_bytes(int N, int H, int W, int levels);
+long c2m_flow_workspace_offset(int N, int H, int W, int levels, int what, int level);
+int c2m_flow_pyramid(const void* a, const void* b, int dt, float lo, float hi, int N, int H, int W, int levels,
+                     void* workspace, long workspace_bytes, void* stream);
+int c2m_flow_patch_search(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
+                          int init_shift, float* records, long record_elems, int N, int h, int w, int iters, void* stream);
+int c2m_flow_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
+                     float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, void* stream);
+
 /* ---- predicted frames at dataset resolution (detail_warp.hip): c2m_amd.fullres ---------------------------------------------
  * The reference has no counterpart.  frame [B][H][W][3] uint8 is the last input frame at the output size; generated, warped
  * [B][3][T][h][w], flow [B][2][T][h][w] (working-size pixels) and occ [B][1][T][h][w] (NULL: 1 everywhere) are dense fp32 at the
