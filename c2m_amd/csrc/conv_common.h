@@ -46,7 +46,6 @@ struct ConvP {
     // [class][tap][16-channel chunk][half][Mpad rows] 16-byte units, ktab = [class][ntaps] {dt, dy, dx, 1}
     int g8_nch, g8_ntaps, g8_CB, g8_Mpad;
     unsigned g8_a_bytes, g8_plane_bytes;      // bytes of ONE class image; bytes of one channel-block plane
-    int g8_dbg;                               // tuning only (geom[95] >> 8): 1 = no K loop, 2 = no stores
 };
 
 struct WgradP {

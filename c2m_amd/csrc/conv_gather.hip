@@ -34,8 +34,7 @@ __global__ __launch_bounds__(256, WGS) void conv_gather_nc8_kernel(const ConvP p
     const int cls = p.ncls > 1 ? (int)blk.z / p.splits : 0;
     const int split = p.ncls > 1 ? (int)blk.z - cls * p.splits : (int)blk.z;
     const int k_beg = split * p.ksteps_per_split;
-    int k_end = k_beg + p.ksteps_per_split; k_end = k_end < p.nk ? k_end : p.nk;
-    if (p.g8_dbg & 1) k_end = k_beg;
+    const int k_end = k_beg + p.ksteps_per_split < p.nk ? k_beg + p.ksteps_per_split : p.nk;
     const int nch = p.g8_nch, ntaps = p.g8_ntaps;
 
     if (tid < ntaps) s_taps[tid] = p.ktab[cls * ntaps + tid];
@@ -152,7 +151,6 @@ __global__ __launch_bounds__(256, WGS) void conv_gather_nc8_kernel(const ConvP p
 
     // ---- epilogue: the mappings of conv_igemm_kernel with one row block of BM and the wave's 64 pixel columns; buffer stores with
     // per-pixel offsets for both targets (conv_store.h), rows past M masked per lane in the last row tile
-    if ((p.g8_dbg & 2) && acc[0][0][0] != 12345.f) return;
     const bool direct = p.splits == 1;
     const bool yh = p.yh && direct;
     const int yes = yh ? 2 : 4;
@@ -192,24 +190,21 @@ __global__ __launch_bounds__(256, WGS) void conv_gather_nc8_kernel(const ConvP p
     }
 }
 
-// variant: geom[95] & 255 (0 = the rule below); p.g8_* are filled and validated by c2m_conv_igemm
+// variant: geom[C2M_G_G8_VARIANT] (0 = the rule below, or one of the rule's choices 1, 3, 5); p.g8_* are filled and validated by c2m_conv_igemm
 int c2m_launch_gather_nc8(const ConvP& p, int variant, int splits, hipStream_t s) {
     const unsigned ptiles = (unsigned)c2m_cdiv(p.Npix, 256);
     int v = variant;
-    // (kernel trace of tools/ab_g8.py on one box, all variants per shape: 64-row tiles 2 stages x 3 workgroups per CU >= 3 stages x 2
-    // everywhere (45-row (4,4,4) data gradient 160 vs 209 us); 128-row tiles: variants 3 / 6 within 3 %; <= 32 rows: 4 K-steps per stage)
+    // (kernel trace on one box, seven variants per shape: 64-row tiles 2 stages x 3 workgroups per CU >= 3 stages x 2 everywhere
+    // (45-row (4,4,4) data gradient 160 vs 209 us); 128-row tiles: 3 stages of 2 K-steps within 3 % of 4 stages of 1; <= 32 rows:
+    // 4 K-steps per stage.  The losers are no longer instantiated; the numbers of the survivors are unchanged.)
     if (v == 0) v = p.M <= 32 ? 1 : ((p.M <= 64 || (p.M % 128 >= 1 && p.M % 128 <= 64)) ? 5 : 3);
 #define G8_LAUNCH(BM, UU, NB, WG) do {                                                                                     \
         dim3 grid(ptiles * (unsigned)c2m_cdiv(p.M, BM) * (unsigned)(splits * p.ncls));                                      \
         hipLaunchKernelGGL((conv_gather_nc8_kernel<BM, UU, NB, WG>), grid, dim3(256), 0, s, p); } while (0)
     switch (v) {
         case 1: G8_LAUNCH(32, 4, 2, 2); break;         // (rows, K-steps per stage, stages, workgroups per CU)
-        case 2: G8_LAUNCH(64, 2, 3, 2); break;
         case 3: G8_LAUNCH(128, 2, 3, 2); break;
-        case 4: G8_LAUNCH(64, 1, 4, 3); break;
         case 5: G8_LAUNCH(64, 2, 2, 3); break;
-        case 6: G8_LAUNCH(128, 1, 4, 2); break;
-        case 7: G8_LAUNCH(32, 2, 3, 2); break;
         default: return (int)hipErrorInvalidValue;
     }
 #undef G8_LAUNCH

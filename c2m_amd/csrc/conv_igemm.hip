@@ -651,7 +651,7 @@ C2M_API int c2m_conv_igemm(const float* A, const void* X, void* Y, void* Y_inter
     if (g[C2M_G_G8] == 1) {
         // NC8 gather form (conv_gather_nc8_kernel): X = NC8 of the gathered bf16 tensor ([N][ceil(C/8)][Ti*Hi*Wi][8], geom[32] its bytes),
         // A = c2m_pack_weights_bf16_gather image(s) of this launch's first class, ktab = [ncls][taps] {dt, dy, dx, 1}, nk = taps *
-        // ceil(C/16) K-steps in (tap, chunk) order; C = geom[28], taps = geom[29]; geom[95] = tile variant (0 = rule)
+        // ceil(C/16) K-steps in (tap, chunk) order; C = geom[28], taps = geom[29]; geom[C2M_G_G8_VARIANT] = tile variant (0 = rule, or 1 | 3 | 5)
         const int C = (int)g[C2M_G_CIN], taps = (int)g[C2M_G_TAPS];
         if (g[C2M_G_PRECISION] != 1 || !p.xh || g[C2M_G_PATCH] || C <= 0 || taps <= 0 || taps > 64 || (((uintptr_t)A | (uintptr_t)X) & 15))
             return (int)hipErrorInvalidValue;
@@ -661,8 +661,8 @@ C2M_API int c2m_conv_igemm(const float* A, const void* X, void* Y, void* Y_inter
         if (plane * p.g8_CB > (long)p.x_bytes || p.x_bytes % (plane * p.g8_CB) || ab * p.ncls >= 0x80000000LL)
             return (int)hipErrorInvalidValue;
         p.g8_plane_bytes = (unsigned)plane; p.g8_a_bytes = (unsigned)ab;
-        p.g8_dbg = (int)(g[C2M_G_G8_VARIANT] >> 8);
-        return c2m_launch_gather_nc8(p, (int)g[C2M_G_G8_VARIANT] & 255, splits, s);
+        if (g[C2M_G_G8_VARIANT] < 0 || g[C2M_G_G8_VARIANT] > 5) return (int)hipErrorInvalidValue;
+        return c2m_launch_gather_nc8(p, (int)g[C2M_G_G8_VARIANT], splits, s);
     }
     if (g[C2M_G_PATCH]) {                                           // LDS-patch path (3x3 stride 1, chosen by the host plan)
         if (ns != 1 || p.st != 1 || p.sh != 1 || p.sw != 1) return (int)hipErrorInvalidValue;

@@ -19,7 +19,6 @@
 #include "dtype.h"
 #include "conv_store.h"
 #include "conv_types.h"
-#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 
@@ -465,12 +464,13 @@ C2M_API int c2m_conv_patch_nc8(const void* A, const void* X, void* Y, void* Y_in
     p.chunks_per_split = c2m_cdiv(p.nchunks, splits);
     if (c2m_cdiv(p.nchunks, p.chunks_per_split) != splits) return (int)hipErrorInvalidValue;
     p.T = 1; p.nch2d = p.nchunks; p.t0 = 0; p.treflect = 0; p.out_st = 0; p.ptab = nullptr;
+    if (g[C2M_G_NC8_VARIANT] < 0 || g[C2M_G_NC8_VARIANT] > 5) return (int)hipErrorInvalidValue;
     return nc8_launch_patch(p, splits, (int)g[C2M_G_NC8_VARIANT], (hipStream_t)stream);
 }
 
 static int nc8_launch_patch(Nc8P& p, int splits, int v, hipStream_t s) {
-    // tile / buffering variant (tuning): 0 = rule below; (output rows, LDS buffers, workgroups per CU, tile rows):
-    // 1 (64, 2, 2, 8)   2 (64, 2, 2, 16)   3 (128, 3, 1, 8)   4 (32, 3, 2, 8)   5 (32, 2, 2, 16)   6 (64, 3, 1, 16)
+    // tile / buffering variant: 0 = rule below, or one of the rule's choices (output rows, LDS buffers, workgroups per CU, tile rows):
+    // 1 (64, 2, 2, 8)   2 (64, 2, 2, 16)   4 (32, 3, 2, 8)   5 (32, 2, 2, 16)
     if (v == 0) {
         // 16-row tiles (half the weight traffic per MFMA, twice the work between barriers) where they still give two full rounds
         // of workgroups (512 resident: 256 CUs x 2); measured per shape on one box (tools/ab_nc8.py): 938-986 vs 883-910 TF/s on
@@ -487,10 +487,8 @@ static int nc8_launch_patch(Nc8P& p, int splits, int v, hipStream_t s) {
     switch (v) {
         case 1: NC8_LAUNCH(64, 2, 2, 8); break;
         case 2: NC8_LAUNCH(64, 2, 2, 16); break;
-        case 3: NC8_LAUNCH(128, 3, 1, 8); break;
         case 4: NC8_LAUNCH(32, 3, 2, 8); break;
         case 5: NC8_LAUNCH(32, 2, 2, 16); break;
-        case 6: NC8_LAUNCH(64, 3, 1, 16); break;
         default: return (int)hipErrorInvalidValue;
     }
 #undef NC8_LAUNCH
@@ -834,7 +832,7 @@ static void wgrad_nc8_shape(int M, int C, long N, int H, int W, int s2, int& Mp,
     Mp = c2m_cdiv(M, 64) * 64; Cp = c2m_cdiv(C, 32) * 32;
     nchunks = N * c2m_cdiv(H, 4) * c2m_cdiv(W, 32);
     const long tiles = (long)(Mp / 64) * (Cp / 32) * (s2 ? 2 : 1);
-    static const long target = getenv("C2M_WGRAD_NC8_WGS") ? atol(getenv("C2M_WGRAD_NC8_WGS")) : 768;      // (tuning knob)
+    const long target = 768;
     long s = (target + tiles - 1) / tiles;                        // ~1.5 resident rounds of 512 workgroups ...
     // ... but >= 16 chunks (2048 pixels, ~10 us of MFMAs) per split: every workgroup writes a 73 KB slab that is read back
     const long maxs = nchunks / 16 > 0 ? nchunks / 16 : 1;

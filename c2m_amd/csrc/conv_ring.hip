@@ -20,6 +20,9 @@
 // corner), one thread per row -- sums their seven (tap, dY element) products over the channels.  So every element of dX has
 // exactly one writer in this launch: the read-modify-write needs no atomics and the result is bit-repeatable.  No padded scratch
 // tensor, no separate fold pass.
+// That is the FIRST form (c2m_reflect_ring_dgrad, kept as the second implementation the tests compare).  The product runs the
+// buffer form (c2m_reflect_ring_buffer, at the end of this file): the same GEMM part writes its terms to a compact buffer, the row
+// sides carry the corners, and the Winograd launch behind it adds them in its epilogue -- no read-modify-write, no corner part.
 //
 // GEMM part: one workgroup = one side x 64 line positions (pixels: images x positions, tiles may span images) x up to 256 rows.
 // The column sides read ONE useful float per 128-byte line of dY (elements W floats apart), and a fully divergent load costs the
@@ -29,7 +32,6 @@
 // -- and serve all the rows of the workgroup: 6-12x fewer line requests per CU.
 #include "common.h"
 #include "conv_types.h"
-#include <stdlib.h>
 
 constexpr int RG_CK = 16;            // channels per chunk
 constexpr int RG_PX = 64;            // pixels (line positions x images) per workgroup of a row side; column sides: 32
@@ -44,7 +46,6 @@ struct RingP {
     int nchunks, mt32, mgroups;      // 16-channel chunks, 32-row tiles, row groups of 128 * MTW rows
     int pt[4];                       // pixel tiles of 64 per side
     int gemm_blocks, corner_blocks;
-    int diag;                        // timing diagnostics (C2M_RING_DIAG): 1 no epilogue, 2 no MFMAs, 4 no dY gathers, 8 no A loads
     unsigned dy_bytes;
 };
 
@@ -79,9 +80,11 @@ C2M_API int c2m_ring_pack(const float* w, float* apack, int C, int M, void* stre
 
 constexpr int RG_SP = 72;            // LDS pitch of a channel's 66-element slice
 
-// MTW = 32-row tiles per wave: the workgroup's four waves cover 128 * MTW rows of ALL 64 pixels
+// MTW = 32-row tiles per wave: the workgroup's four waves cover 128 * MTW rows of ALL 64 pixels.  Only MTW = 1 is instantiated:
+// the column sides are bound by their divergent gathers and read-modify-writes (one 128-byte line per element), which only more
+// workgroups spread -- 256-row groups (MTW = 2) halved them and measured slower.
 template <int MTW>
-__global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kernel(const RingP p) {
+__global__ __launch_bounds__(256, 2) void reflect_ring_dgrad_kernel(const RingP p) {
     __shared__ float sS[2][RG_CK][RG_SP];            // 2 x 16 channels x (pixel p0 - 1 .. p0 + 64) of the side's line(s)
     __shared__ float sD[7][RG_CK];                   // corner part: the seven dY elements of 16 channels
     const int tid = threadIdx.x, lane = tid & 63;
@@ -195,18 +198,17 @@ __global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kern
             const int q = q2 * NSUB + sub;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (p.diag & 4) break;
                 const int c = q * RG_CK + cg * 4 + e;         // wave-uniform; chunks past the end: c >= C -> zeros
                 sraw[sub][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsy, c < p.C ? voff_main : C2M_OOB, c * HW * 4, 0));
             }
-            if (wave == 0 && !(p.diag & 4)) {
+            if (wave == 0) {
                 const int c = q * RG_CK + (tid & 15);
                 hraw[sub] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                     rsy, (c < p.C && voff_halo != C2M_OOB) ? voff_halo + (unsigned)(c * HW * 4) : C2M_OOB, 0, 0));
             }
 #pragma unroll
             for (int k = 0; k < MTW; ++k) {
-                const bool live = t32_0 + k < p.mt32 && q < p.nchunks && !(p.diag & 8);
+                const bool live = t32_0 + k < p.mt32 && q < p.nchunks;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     if (live) {
@@ -247,7 +249,6 @@ __global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kern
                 for (int j = 0; j < 3; ++j) { a[sub][k][j][0] = araw[sub][k][j][0]; a[sub][k][j][1] = araw[sub][k][j][1]; }
         __syncthreads();
         if (q2 + 1 < niter) fetch(q2 + 1);                     // in flight during this iteration's MFMAs
-        if (p.diag & 2) continue;
 #pragma unroll
         for (int sub = 0; sub < NSUB; ++sub) {
             const float* __restrict__ bb = &sS[sub][lane >> 5][(lane & 31) + 2];
@@ -271,7 +272,6 @@ __global__ __launch_bounds__(256, MTW == 1 ? 2 : 1) void reflect_ring_dgrad_kern
             }
         }
     }
-    if (p.diag & 1) return;
     // ---- dX[target] += acc: lane owns pixel column (lane & 31) of each half, rows 4 (lane >> 5) + (r & 3) + 8 (r >> 2)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -320,24 +320,14 @@ static int ring_launch(const float* apack, const float* dY, float* dX, float* R,
     p.A = apack; p.dY = dY; p.dX = dX; p.R = R; p.r_l = r_l;
     p.N = N; p.C = C; p.M = M; p.H = H; p.W = W;
     p.nchunks = c2m_cdiv(C, RG_CK); p.mt32 = c2m_cdiv(M, 32);
-    // 128 rows per workgroup (MTW = 1): the column sides are bound by their divergent gathers and read-modify-writes (one 128-byte
-    // line per element), which only more workgroups spread -- 256-row groups (MTW = 2) halved them and measured slower
-    const int mtw = 1;
-    p.mgroups = c2m_cdiv(p.mt32, 4 * mtw);
+    p.mgroups = c2m_cdiv(p.mt32, 4);                            // 128 rows per workgroup (MTW = 1)
     p.pt[0] = p.pt[1] = c2m_cdiv((long)N * W, 64);
     p.pt[2] = p.pt[3] = c2m_cdiv((long)N * H, 32);
     p.gemm_blocks = (p.pt[0] + p.pt[1] + p.pt[2] + p.pt[3]) * p.mgroups;
     p.corner_blocks = R ? 0 : N * 4;                            // buffer mode: the row terms carry the corners (see the kernel)
     p.dy_bytes = (unsigned)dy_bytes;
-    static const int diag = [] { const char* e = getenv("C2M_RING_DIAG"); return e ? atoi(e) : 0; }();
-    p.diag = diag;
-    static const int part = [] { const char* e = getenv("C2M_RING_PART"); return e ? atoi(e) : 0; }();      // timing diagnostics only
-    if (part == 1) p.corner_blocks = 0;                         // GEMM part only (wrong corner targets)
-    if (part == 2) { p.gemm_blocks = 0; p.pt[0] = p.pt[1] = p.pt[2] = p.pt[3] = 0; }      // corner part only
-    if (p.corner_blocks + p.gemm_blocks == 0) return 0;
     const dim3 grid((unsigned)(p.corner_blocks + p.gemm_blocks));
-    if (mtw == 1) hipLaunchKernelGGL(reflect_ring_dgrad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
-    else          hipLaunchKernelGGL(reflect_ring_dgrad_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(reflect_ring_dgrad_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 

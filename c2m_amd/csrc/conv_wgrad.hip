@@ -6,7 +6,6 @@
 //
 // c2m_conv_wgrad also launches the <= 4-row vector-ALU forms (conv_thin.hip), which write the same slab layout.
 #include "conv_common.h"
-#include <stdlib.h>
 
 template <int BM, int BN, int WGM, int WGN, int NS, bool BF = false>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradP p) {
@@ -642,12 +641,12 @@ C2M_API int c2m_conv_wgrad(const void* dY, const void* X, float* slab, float* dW
         const dim3 grid(p.J / BN, c2m_cdiv(p.M, BM), Seff);
         const dim3 grid1(grid.x * grid.y * grid.z);       // 1-D launch, decoded XCD-aware in the kernel (common.h)
         // g[C2M_G_WGRAD_WIDE] = 1: the layer qualifies for the 16-byte-load form (host: unit x stride, Wi == Wo, Wo % 8 == 0, |tap dx| <= 1)
-        if (bf16 && g[C2M_G_WGRAD_WIDE] == 2 && !getenv("C2M_WGRAD_NARROW")) {      // the stride-2 form (host: sw == 2, Wi == 2 Wo, Wo % 8 == 0, dx in -1 .. 2)
+        if (bf16 && g[C2M_G_WGRAD_WIDE] == 2) {      // the stride-2 form (host: sw == 2, Wi == 2 Wo, Wo % 8 == 0, dx in -1 .. 2)
             if (p.sw != 2 || p.Wi != 2 * p.Wo || (p.Wo & 7) || (p.dy_sc & 7) || (p.pix_per_split & 63)) return (int)hipErrorInvalidValue;
             if (p.M <= 32)      hipLaunchKernelGGL((conv_wgrad_wide_bf16_kernel<32, 128, 1, 4, 2>), grid1, dim3(256), 0, s, p, NS);
             else if (p.M > 64)  hipLaunchKernelGGL((conv_wgrad_wide_bf16_kernel<128, 128, 2, 2, 2>), grid1, dim3(256), 0, s, p, NS);
             else                hipLaunchKernelGGL((conv_wgrad_wide_bf16_kernel<64, WG64_BN, 2, 2, 2>), grid1, dim3(256), 0, s, p, NS);
-        } else if (bf16 && g[C2M_G_WGRAD_WIDE] == 1 && !getenv("C2M_WGRAD_NARROW")) {
+        } else if (bf16 && g[C2M_G_WGRAD_WIDE] == 1) {
             if (p.sw != 1 || p.Wi != p.Wo || (p.Wo & 7) || p.Wi < 8 || (p.dy_sc & 7) || (p.pix_per_split & 63)) return (int)hipErrorInvalidValue;
             if (p.M <= 32)      hipLaunchKernelGGL((conv_wgrad_wide_bf16_kernel<32, 128, 1, 4>), grid1, dim3(256), 0, s, p, NS);
             else if (p.M > 64)  hipLaunchKernelGGL((conv_wgrad_wide_bf16_kernel<128, 128, 2, 2>), grid1, dim3(256), 0, s, p, NS);

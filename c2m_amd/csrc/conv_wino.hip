@@ -17,7 +17,6 @@
 // applies bias + activation and writes coalesced NCHW rows.
 #include "common.h"
 #include "conv_types.h"
-#include <stdlib.h>
 
 struct WinoP {
     const float* U;      // packed filter transform (see wino_filter_kernel)
@@ -643,12 +642,9 @@ C2M_API int c2m_wino_filter_transform(const float* w, float* upack, int Cout, in
 // Region shape of a launch over an Ho x Wo output domain: the fixed 4 x 8 tiles (8 x 16 outputs; 16-byte-store epilogue)
 // unless another th x tw (th*tw <= 32 tile columns of the MFMA, (2th+2)(2tw+2) <= 192 = three DMA rows of patch positions)
 // covers the domain with at most 0.9x the regions.  Ties: the wider shape (longer contiguous rows).
-// C2M_WINO_SHAPE=fixed pins 4 x 8 (A/B).
 static void wino_region_shape(int Ho, int Wo, int* th, int* tw) {
-    static const bool fixed = [] { const char* e = getenv("C2M_WINO_SHAPE"); return e && e[0] == 'f'; }();
     *th = WR / 2; *tw = WC / 2;
     const long base = (long)c2m_cdiv(Ho, WR) * c2m_cdiv(Wo, WC);
-    if (fixed) return;
     long best = base;
     for (int a = 1; a <= 16; ++a)
         for (int b = 1; b <= 32; ++b) {
@@ -1282,18 +1278,15 @@ __global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const f32x4* __r
 // Input-channel tile of the launch: 32 (NI = 1: 64 x 32 channels, 128 accumulators, two workgroups per CU).  The 64 x 64
 // tile with one workgroup per CU (NI = 2) was 8...13 % slower on every eligible shape (tools/ab_wino_wgrad.py, first
 // version of the kernel) and is no longer instantiated.
-static int wino_wg_ni(int M, int K) { (void)M; (void)K; return 1; }
 
 C2M_API int c2m_wino_wgrad_splits(int M, int K, int nimg, int H, int W) {
     const long regions = (long)nimg * (H / GR) * (W / GC);
-    const int ni = wino_wg_ni(M, K);
     const int mrows = M <= 32 ? 32 : 64;        // 32-row variant for Cout <= 32 (three workgroups per CU)
-    const long tiles = (long)c2m_cdiv(M, mrows) * c2m_cdiv(K, 32 * ni);
-    long S = (mrows == 32 ? 768 : (ni == 1 ? 512 : 256)) / tiles;     // one resident round: 256 CUs x (3 | 2 | 1) workgroups
+    const long tiles = (long)c2m_cdiv(M, mrows) * c2m_cdiv(K, 32);
+    long S = (mrows == 32 ? 768 : 512) / tiles;     // one resident round: 256 CUs x (3 | 2) workgroups
     if (S < 1) S = 1;
     const long maxS = (regions + 15) / 16;      // >= 16 regions (128 tiles) per split
     if (S > maxS) S = maxS;
-    if (const char* f = getenv("C2M_WINO_WG_SPLITS")) { const long v = atol(f); if (v > 0) S = v < regions ? v : regions; }
     if (S < 1) S = 1;
     const long per = (regions + S - 1) / S;
     return (int)((regions + per - 1) / per);
@@ -1315,9 +1308,8 @@ static int wino_wgrad_launch(const float* dY, const float* X, float* slab, float
     p.regions = nimg * (H / GR) * (W / GC);
     const int S = c2m_wino_wgrad_splits(M, K, nimg, H, W);
     p.per_split = c2m_cdiv(p.regions, S);
-    const int ni = wino_wg_ni(M, K);
     const int mrows = M <= 32 ? 32 : 64;
-    dim3 grid((unsigned)S * c2m_cdiv(M, mrows) * c2m_cdiv(K, 32 * ni));
+    dim3 grid((unsigned)S * c2m_cdiv(M, mrows) * c2m_cdiv(K, 32));
     hipStream_t s = (hipStream_t)stream;
     if (mrows == 32) hipLaunchKernelGGL((conv_wino_wgrad_kernel<1, 1, 3>), grid, dim3(256), 0, s, p);
     else             hipLaunchKernelGGL((conv_wino_wgrad_kernel<1, 2, 2>), grid, dim3(256), 0, s, p);
@@ -1325,8 +1317,7 @@ static int wino_wgrad_launch(const float* dY, const float* X, float* slab, float
     if (rc) return rc;
     const long n = 16L * M * K;
     float* usum = slab + (long)S * n;
-    static const bool two_stage = getenv("C2M_WINO_WGRAD_TWO_STAGE") != nullptr;      // A/B knob
-    if (S <= 64 && (M & 3) == 0 && !two_stage) {
+    if (S <= 64 && (M & 3) == 0) {
         const int cblocks = ((M >> 2) + 15) / 16;
         hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3((unsigned)(K * cblocks)), dim3(256), 0, s, (const f32x4*)slab, dbslab,
                            dW, db, M, K, S);

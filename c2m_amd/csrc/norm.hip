@@ -257,13 +257,14 @@ __global__ __launch_bounds__(256) void norm_apply_vec_kernel(const ApplyP<T> p, 
     }
 }
 
-// ------------------------------------------------------------------------------------------- NC8 side output (round 4)
-// bf16 data path: the normalised activation feeds a channel-blocked convolution (conv_nc8.hip), so the apply pass writes it in BOTH
-// layouts at once -- NCHW for everybody else, NC8 ([N][C/8][S][8], the 8 channels of a pixel in one 16-byte unit) for that conv --
-// instead of a separate c2m_nchw_to_nc8 pass over the tensor (one read of it less; the layout passes were 3.3 / 5.9 ms of a
-// configs[3] / configs[2] step).  A thread owns 8 consecutive pixels of 8 consecutive channels: eight 16-byte loads, the per-channel
-// arithmetic of norm_apply_vec_kernel, eight 16-byte NCHW stores, an 8x8 transpose of bf16 pairs in registers (v_perm_b32), eight
-// 16-byte NC8 stores (128 contiguous bytes).  Same values bit for bit in both outputs.
+// ------------------------------------------------------------------------------------------- NC8 output (round 4)
+// bf16 data path: where the normalised activation feeds ONLY a channel-blocked convolution (conv_nc8.hip), the apply pass writes it
+// in NC8 ([N][C/8][S][8], the 8 channels of a pixel in one 16-byte unit) INSTEAD of NCHW, and no c2m_nchw_to_nc8 pass over the tensor
+// runs (the layout passes were 3.3 / 5.9 ms of a configs[3] / configs[2] step).  A thread owns 8 consecutive pixels of 8 consecutive
+// channels: eight 16-byte loads, the per-channel arithmetic of norm_apply_vec_kernel, an 8x8 transpose of bf16 pairs in registers
+// (v_perm_b32), eight 16-byte NC8 stores (128 contiguous bytes): bit for bit c2m_nchw_to_nc8 of the NCHW result.  (Writing BOTH
+// layouts from one launch measured slower than the layout passes it saved -- 47.7 vs 47.05 ms, 71.5 vs 70.7 ms per step -- and is
+// not offered.)
 __device__ __forceinline__ void nc8_transpose_store(const unsigned (&r)[8][4], uint4* __restrict__ dst) {
 #pragma unroll
     for (int px = 0; px < 8; ++px) {
@@ -292,7 +293,6 @@ __device__ __forceinline__ unsigned nc8_pack2(float a, float b) {
 __global__ __launch_bounds__(256) void norm_apply_nc8_kernel(const ApplyP<bf16_t> p, uint4* __restrict__ yn, int CB, long S8, long total) {
     const uint4* __restrict__ x4 = reinterpret_cast<const uint4*>(p.x);
     const uint4* __restrict__ g4 = reinterpret_cast<const uint4*>(p.gb);
-    uint4* __restrict__ y4 = reinterpret_cast<uint4*>(p.y);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long g = i % S8, ncb = i / S8;
         const int cb = (int)(ncb % CB), n = (int)(ncb / CB);
@@ -322,7 +322,6 @@ __global__ __launch_bounds__(256) void norm_apply_nc8_kernel(const ApplyP<bf16_t
                 for (int e = 0; e < 8; ++e) o[e] = c2m_act((xv[e] - mean) * invstd * sc[e] + sh[e], p.act, p.slope);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[j][e] = nc8_pack2(o[2 * e], o[2 * e + 1]);
-                if (y4) y4[plane * S8 + g] = make_uint4(r[j][0], r[j][1], r[j][2], r[j][3]);      // (NULL: the NC8 form is the only output)
             }
         }
         nc8_transpose_store(r, yn + (((long)n * CB + cb) * S8 + g) * 8);
@@ -334,7 +333,8 @@ static inline bool norm_vec_ok(long S, const void* a, const void* b, const void*
            c2m_aligned(dt == C2M_BF16 ? 8 : 16, a, b, c, d);
 }
 
-// y_nc8 (optional, bf16 tensors with S % 8 == 0 only): the same result in the channel-blocked layout of conv_nc8.hip as well.
+// y_nc8 (bf16 tensors with S % 8 == 0 only): the result in the channel-blocked layout of conv_nc8.hip INSTEAD of y -- exactly one of
+// y, y_nc8 is given; both: hipErrorInvalidValue.
 C2M_API int c2m_norm_apply(const void* x, const float* mean, const float* invstd, const float* gamma,
                            const float* beta, const void* gb, void* y, void* y_nc8, int N, int C, long S, int mode, int act,
                            float slope, int dt, void* stream) {
@@ -342,9 +342,9 @@ C2M_API int c2m_norm_apply(const void* x, const float* mean, const float* invstd
     const long total = (long)N * C * S;
     if (total <= 0) return 0;
     if (y_nc8) {
-        if (dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, y, gb, y_nc8))
+        if (y || dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, gb, y_nc8))
             return (int)hipErrorInvalidValue;
-        ApplyP<bf16_t> p{(const bf16_t*)x, mean, invstd, gamma, beta, (const bf16_t*)gb, (bf16_t*)y, N, C, S, mode, act, slope};
+        ApplyP<bf16_t> p{(const bf16_t*)x, mean, invstd, gamma, beta, (const bf16_t*)gb, nullptr, N, C, S, mode, act, slope};
         const int CB = (C + 7) / 8;
         const long n8 = (long)N * CB * (S / 8);
         hipLaunchKernelGGL(norm_apply_nc8_kernel, dim3(c2m_grid(n8, 256)), dim3(256), 0, (hipStream_t)stream, p, (uint4*)y_nc8, CB, S / 8, n8);
@@ -764,12 +764,11 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_vec_kernel(const BwdP<T> p
     }
 }
 
-// dx of the norm in both layouts (see norm_apply_nc8_kernel): the gradient it hands back is the dY of the convolution in front.
+// dx of the norm in NC8 form (see norm_apply_nc8_kernel): the gradient it hands back is the dY of the convolution in front.
 __global__ __launch_bounds__(256) void norm_bwd_apply_nc8_kernel(const BwdP<bf16_t> p, uint4* __restrict__ dxn, int CB, long S8, long total) {
     const uint4* __restrict__ x4 = reinterpret_cast<const uint4*>(p.x);
     const uint4* __restrict__ gy4 = reinterpret_cast<const uint4*>(p.gy);
     const uint4* __restrict__ g4 = reinterpret_cast<const uint4*>(p.gb);
-    uint4* __restrict__ d4 = reinterpret_cast<uint4*>(p.dx);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const long g = i % S8, ncb = i / S8;
         const int cb = (int)(ncb % CB), n = (int)(ncb / CB);
@@ -804,7 +803,6 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_nc8_kernel(const BwdP<bf16
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) r[j][e] = nc8_pack2(o[2 * e], o[2 * e + 1]);
-                if (d4) d4[plane * S8 + g] = make_uint4(r[j][0], r[j][1], r[j][2], r[j][3]);      // (NULL: dx exists in NC8 form only)
             }
         }
         nc8_transpose_store(r, dxn + (((long)n * CB + cb) * S8 + g) * 8);
@@ -922,13 +920,15 @@ __global__ __launch_bounds__(256) void norm_bn_small_bwd_fused_kernel(const BwdP
 }
 
 // workspace floats: N*C*chunks*2 (partials) + nstat*2 (coefficients)  <= c2m_norm_workspace_floats(N, C, S)
-// dx_nc8 (optional, bf16 tensors with S % 8 == 0 only): dx in the channel-blocked layout as well (see c2m_norm_apply).
+// dx_nc8 (bf16 tensors with S % 8 == 0 only): dx in the channel-blocked layout INSTEAD of dx (see c2m_norm_apply); both given:
+// hipErrorInvalidValue.
 C2M_API int c2m_norm_bwd(const void* x, const void* gy, const float* mean, const float* invstd, const float* gamma,
                          const float* beta, const void* gb, void* ggb, float* dgamma, float* dbeta, void* dx, void* dx_nc8,
                          float* workspace, int N, int C, long S, int mode, int act, float slope, int dt, void* stream) {
     C2M_ENTER();
     const long total = (long)N * C * S;
     if (total <= 0) return 0;
+    if (dx && dx_nc8) return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     const bool vec = norm_vec_ok(S, x, gy, gb, dx, dt);
     C2M_DISPATCH_DT(dt,
@@ -962,13 +962,13 @@ C2M_API int c2m_norm_bwd(const void* x, const void* gy, const float* mean, const
         else
             hipLaunchKernelGGL(norm_bwd_apply_kernel<T>, dim3(c2m_grid(total, 256)), dim3(256), 0, s, p););
     if (dx_nc8) {
-        if (dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, gy, gb, dx, dx_nc8))
+        if (dt != C2M_BF16 || (S & 7) || !c2m_aligned(16, x, gy, gb, dx_nc8))
             return (int)hipErrorInvalidValue;
         BwdP<bf16_t> p;
         p.x = (const bf16_t*)x; p.gy = (const bf16_t*)gy; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
         p.gb = (const bf16_t*)gb; p.ggb = (bf16_t*)ggb; p.chunks = norm_chunks(S);
         p.partial = workspace; p.coef = workspace + (long)N * C * p.chunks * 2;
-        p.dgamma = dgamma; p.dbeta = dbeta; p.dx = (bf16_t*)dx;
+        p.dgamma = dgamma; p.dbeta = dbeta; p.dx = nullptr;
         p.N = N; p.C = C; p.S = S; p.mode = mode; p.act = act; p.slope = slope;
         const int CB = (C + 7) / 8;
         const long n8 = (long)N * CB * (S / 8);

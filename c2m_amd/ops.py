@@ -107,16 +107,14 @@ _geom_cache = {}
 _conv_bf16 = False
 # minimum region fill of a Winograd data-gradient launch: the padded 18x34 domain of the 16x32 reflect layers fills 53 % of its
 # 8x16 regions and still beats the gather kernel by 14-30 % (tools/run_conv.py A/B); the 10x18 domain (35 %) does not
-_WINO_DFIT = float(os.environ.get("C2M_WINO_DFIT", "0.5"))
-_WINO_MIN_WGS = int(os.environ.get("C2M_WINO_MIN_WGS", "128"))   # smallest Winograd forward / dgrad grid: 160 workgroups of a 1536-deep layer still beat the gather kernel 1.5x
-_WGRAD_WIDE_S2 = os.environ.get("C2M_WGRAD_WIDE_S2", "1") != "0"      # bf16 stride-2 weight gradient on the 16-byte-load kernel (A/B knob)
-_WINO_TPAIRS = os.environ.get("C2M_WINO_TPAIRS", "1") != "0"    # 3x3x3 reflect data gradient over unpadded frames (A/B knob)
-# reflect-padded 3x3 data gradients as interior (exact domain, Winograd) + pad ring (conv_ring.hip): "auto" (maps of >= C2M_RING_MIN_PIX
+_WINO_DFIT = 0.5
+_WINO_MIN_WGS = 128   # smallest Winograd forward / dgrad grid: 160 workgroups of a 1536-deep layer still beat the gather kernel 1.5x
+# reflect-padded 3x3 data gradients as interior (exact domain, Winograd) + pad ring (conv_ring.hip): "auto" (maps of >= _RING_MIN_PIX
 # pixels) | "off" (padded domain + two-target epilogue + fold, rounds 1-4) | "force" (tests: every eligible layer with H, W >= 4)
 _RING = os.environ.get("C2M_RING", "auto")
-_RING_BUFFER = os.environ.get("C2M_RING_BUFFER", "1") != "0"     # ring terms through a compact buffer added by the Winograd epilogue (0: in place)
-_RING_MIN_PIX = int(os.environ.get("C2M_RING_MIN_PIX", "1024"))
-_RING_F2_MAX_PIX = int(os.environ.get("C2M_RING_F2_MAX_PIX", "4096"))      # largest map on which an F(2x2) interior + ring beats the padded domain
+_RING_BUFFER = True     # ring terms through a compact buffer added by the Winograd epilogue (False, set by the tests: the first form, in place)
+_RING_MIN_PIX = 1024
+_RING_F2_MAX_PIX = 4096      # largest map on which an F(2x2) interior + ring beats the padded domain
 _WINO4 = os.environ.get("C2M_WINO4", "auto")       # F(4x4,3x3) for the 2-D Winograd layers: "off" | "auto" (rule: _wino4_pays) | "force" (tests: every eligible 2-D Winograd launch)
 _WINO = os.environ.get("C2M_WINOGRAD", "auto")      # "auto" | "off" | "force" (tests: every eligible shape)
 # Winograd WEIGHT gradient (round 2: fragments built in registers from raw LDS patches): "auto" = the layers where it beats
@@ -476,35 +474,27 @@ def _patch_bf16_ok(C, stride, Ho, Wo, M, fill_limit=None, nc8=True):
                           # (nc8: the plan can run it -- planes of whole 8-pixel groups; otherwise the NCHW kernel's own rule below)
         return fill <= (fill_limit or _NC8_FILL)      # (the padded 34x66 domain of a reflect data gradient fills 58 % of its tiles: still 1.5x the gather kernel)
     if C < 128:
-        return (M <= 64 or _PATCH_SMALLC) and fill <= 1.2
+        return M <= 64 and fill <= 1.2
     return fill <= _PATCH_FILL[0] or (fill <= _PATCH_FILL[1] and C >= 256)
 
 
-_NC8_VARIANT = int(os.environ.get("C2M_NC8_VARIANT", "0"))      # tile / buffering variant of conv_patch_nc8_kernel (0 = the library's rule)
-# norm kernels write the NC8 side output for the conv behind / in front.  OFF by default: measured on one box (configs[3] / [2] graph
-# replays) it removes 77 of 174 layout passes (-0.95 ms) but the 8-channel x 8-pixel apply kernels run 2x as long as the per-plane
-# ones they replace (+1.2 ms): 47.7 vs 47.05 ms, 71.5 vs 70.7 ms.  Kept as an A/B knob with its tests (tests/test_gpu_nc8.py).
-_NC8_NORM = os.environ.get("C2M_NC8_NORM", "0") != "0"
+_NC8_VARIANT = 0      # tile / buffering variant of conv_patch_nc8_kernel: 0 = the library's rule; tests set 1, 2, 4, 5 (the rule's choices)
 # NC8 gather kernel (conv_gather_nc8_kernel, conv_gather.hip): every bf16 forward / data gradient the NC8 patch forms do not take
 _NC8_LOG = None
 _NC8_LOG_TAG = [""]          # (tools/nc8_producers.py: what made the gradient tensor a backward conversion sees)
 _NC8_GRAD = os.environ.get("C2M_NC8_GRAD", "1") != "0"      # act_bwd / tap backward write NC8 only where every reader is an NC8 kernel
 _NC8_POISON = os.environ.get("C2M_NC8_POISON", "0") == "1"  # debug: the unused NCHW storage of such gradients is NaN
 _G8 = os.environ.get("C2M_G8", "1") != "0"
-_G8_VARIANT = int(os.environ.get("C2M_G8_VARIANT", "0"))
-_NC8_3D = os.environ.get("C2M_NC8_3D", "1") != "0"           # bf16 3x3x3 layers on the NC8 kernels (A/B knob)
+_G8_VARIANT = 0      # tile variant of conv_gather_nc8_kernel: 0 = the library's rule; tests set 1, 3, 5 (the rule's choices)
 _NC8_S2_WGRAD_MIN_PIX = 16384
-_NC8_S2 = os.environ.get("C2M_NC8_S2", "1") != "0"           # bf16 4x4 stride-2 forward on the parity-plane kernel (A/B knob)
 # padded domains of the reflect data gradients: tile waste above which the NC8 gather form takes them (kernel times on one box,
 # patch kernel with the buffer-store two-target epilogue vs gather form: 66x130 domains, fill 1.34: 78 vs 111 us and 144 vs 151;
 # 34x66, fill 1.71: 106 vs 87; 18x34, fill 2.5: 68 vs 45)
-_NC8_DGRAD_FILL = float(os.environ.get("C2M_NC8_DGRAD_FILL", "1.5"))
-_NC8_S2_FILL_G8 = float(os.environ.get("C2M_NC8_S2_FILL_G8", "1.5"))      # stride-2 patch forms: largest tile waste where the gather form is the alternative
-_NC8_FILL = float(os.environ.get("C2M_NC8_FILL", "2.6"))      # (18x34 padded domains of the 16x32 reflect data gradients: 2.5; still 1.5x+ the gather kernel)
-_NC8_WGRAD = os.environ.get("C2M_NC8_WGRAD", "1") != "0"      # bf16 3x3 weight gradient from NC8 operands (A/B knob)
+_NC8_DGRAD_FILL = 1.5
+_NC8_S2_FILL_G8 = 1.5      # stride-2 patch forms: largest tile waste where the gather form is the alternative
+_NC8_FILL = 2.6      # (18x34 padded domains of the 16x32 reflect data gradients: 2.5; still 1.5x+ the gather kernel)
 _NC8 = os.environ.get("C2M_NC8", "1") != "0"        # bf16 3x3 stride-1 layers on channel-blocked input (A/B knob)
-_PATCH_FILL = tuple(float(v) for v in os.environ.get("C2M_PATCH_FILL", "1.15,1.4").split(","))     # tuning knobs (A/B runs)
-_PATCH_SMALLC = os.environ.get("C2M_PATCH_SMALLC", "0") == "1"
+_PATCH_FILL = (1.15, 1.4)     # bf16 3x3 NCHW patch kernel: largest tile waste (any C; C >= 256), see _patch_pays
 
 
 def _pack_bf16_patch(w, M, C, s_m, s_c, mode=0):
@@ -519,7 +509,7 @@ def _pack_bf16_patch(w, M, C, s_m, s_c, mode=0):
     return out
 
 
-_BF16_SPLIT_DIV = float(os.environ.get("C2M_BF16_SPLIT_DIV", "4"))      # bf16 kernels: a quarter of the fp32 rule's K splits (A/B on configs[2,3], graph mode: 1 -> 60.0 / 93.7 ms, 2 -> 58.4 / 92.5, 4 -> 58.0 / 91.2, no splits -> 65.4 / 98.2)
+_BF16_SPLIT_DIV = 4.0      # bf16 kernels: a quarter of the fp32 rule's K splits (A/B on configs[2,3], graph mode: 1 -> 60.0 / 93.7 ms, 2 -> 58.4 / 92.5, 4 -> 58.0 / 91.2, no splits -> 65.4 / 98.2)
 
 
 def _splits(L, M, nk, npix, bf16):
@@ -661,7 +651,7 @@ def _g8_bm(M):
     return 32 if M <= 32 else (64 if (M <= 64 or 1 <= M % 128 <= 64) else 128)
 
 
-_G8_SPLIT_WGS = int(os.environ.get("C2M_G8_SPLIT_WGS", "320"))
+_G8_SPLIT_WGS = 320
 
 
 def _g8_splits(M, nk, npix, ncls=1):
@@ -766,13 +756,12 @@ def _wino4_pays(L, M, K, nimg, Ho, Wo):
     wgs = regions * (M // 64) if M % 64 == 0 else 0
     if K < _WINO4_MIN_K or M < 64 or fill < _WINO4_MIN_FILL:
         return False
-    return wgs >= _WINO4_MIN_WGS or (K >= 256 and M >= 256 and wgs >= _WINO4_DEEP_WGS)
+    return wgs >= _WINO4_MIN_WGS
 
 
-_WINO4_MIN_K = int(os.environ.get("C2M_WINO4_MIN_K", "64"))
-_WINO4_DEEP_WGS = int(os.environ.get("C2M_WINO4_DEEP_WGS", "1000000"))      # deep (K, M >= 256) layers on small maps: A/B knob, off by default
-_WINO4_MIN_FILL = float(os.environ.get("C2M_WINO4_MIN_FILL", "0.9"))
-_WINO4_MIN_WGS = int(os.environ.get("C2M_WINO4_MIN_WGS", "600"))      # 640 workgroups (256 -> 256 at 32x64, 40 images): 1.12x; 320: 0.8-0.95x
+_WINO4_MIN_K = 64
+_WINO4_MIN_FILL = 0.9
+_WINO4_MIN_WGS = 600      # 640 workgroups (256 -> 256 at 32x64, 40 images): 1.12x; 320: 0.8-0.95x
 
 
 def _wino4_filter(w, Cout, Cin, dgrad):
@@ -949,7 +938,7 @@ class _ConvPlan:
                 o = -2 if reflect else -1
                 # reflect in time: launched over the Ti real frames with the pad frames' contributions as extra (frame, tap)
                 # pairs of the frames they mirror onto (kernel: WinoP::ptab) -- not over Ti + 2 frames + a fold in time
-                self.wino3d_pairs = bool(reflect and Cout % 8 == 0 and To == Ti and Ti >= 2 and _WINO_TPAIRS)
+                self.wino3d_pairs = bool(reflect and Cout % 8 == 0 and To == Ti and Ti >= 2)
                 Tl = Ti if self.wino3d_pairs else Td
                 self.wino_dgrad_target = (N, Cin, Tl, Hd, Wd)
                 self.wino_dgrad_geom = _wino_geom(
@@ -970,11 +959,11 @@ class _ConvPlan:
         self.nc8 = bool(bf16 and _NC8 and nd == 2 and (Hi * Wi) % 8 == 0 and (Ho * Wo) % 8 == 0)
         # ... the 3x3x3 stride-1 pad-1 layers as (sample, frame) images with (time tap, channel) chunks: forward and weight gradient
         # (channel padding up to 45 %: final_fuse has 34 input channels = three 16-channel chunks, still 2x the gather kernel)
-        k333 = bool(bf16 and _NC8 and _NC8_3D and nd == 3 and (kt, kh, kw) == (3, 3, 3) and tuple(stride) == (1, 1, 1) and
+        k333 = bool(bf16 and _NC8 and nd == 3 and (kt, kh, kw) == (3, 3, 3) and tuple(stride) == (1, 1, 1) and
                     (pt, ph, pw) == (1, 1, 1) and (Hi * Wi) % 8 == 0 and Ti >= 2 and Cin >= 12 and _ceil(Cin, 16) <= 1.45 * Cin and
                     Wo >= 32 and Ho >= 8 and (_ceil(Wo, 32) * _ceil(Ho, 8)) <= _NC8_FILL * Wo * Ho)
         self.k333_nc8 = k333 and Cout > 4
-        self.k333_wgrad_nc8 = k333 and _NC8_WGRAD and Cout >= 64 and Cin >= 16
+        self.k333_wgrad_nc8 = k333 and Cout >= 64 and Cin >= 16
         pd = 1 if reflect else 0
         self.k333_dgrad_nc8 = bool(k333 and Cout >= 12 and _ceil(Cout, 16) <= 1.25 * Cout and dM > 4 and
                                    (_ceil(Wi + 2 * pd, 32) * _ceil(Hi + 2 * pd, 8)) <= _NC8_FILL * (Wi + 2 * pd) * (Hi + 2 * pd))
@@ -987,19 +976,19 @@ class _ConvPlan:
         # the same layers measured +0.7 ms with the gather form, configs[3]'s 40-image batches -0.7 ms)
         g8_in = bool(_G8 and Cin >= 12 and _ceil(Cin, 16) <= 1.45 * Cin and in_sc % 8 == 0 and N * osp >= 4096)
         g8_out = bool(_G8 and Cout >= 12 and _ceil(Cout, 16) <= 1.45 * Cout and osp % 8 == 0 and N * osp >= 4096)
-        self.s2_nc8 = bool(self.nc8 and _NC8_S2 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and (ph, pw) == (1, 1)
+        self.s2_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and (ph, pw) == (1, 1)
                            and Hi % 2 == 0 and Wi % 2 == 0 and Cout > 4 and Cin >= 12 and Wo >= 16 and Ho >= 4 and
                            (_ceil(Wo, 32) * _ceil(Ho, 8)) <= (_NC8_S2_FILL_G8 if g8_in else _NC8_FILL) * Wo * Ho)
         # ... their data gradient (four output parity classes over one shared dY patch, one launch)
         qh, qw = Hi // 2 + (1 if reflect else 0), Wi // 2 + (1 if reflect else 0)
-        self.s2_dgrad_nc8 = bool(self.nc8 and _NC8_S2 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
+        self.s2_dgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
                                  (ph, pw) == (1, 1) and Hi % 2 == 0 and Wi % 2 == 0 and Cin >= 8 and Cout >= 12 and qw >= 16 and
                                  dM == Cin and (_ceil(qw, 32) * _ceil(qh, 8)) <= (_NC8_S2_FILL_G8 if (g8_out and dM > 4) else _NC8_FILL) * qw * qh)
-        self.s2_wgrad_nc8 = bool(self.nc8 and _NC8_S2 and _NC8_WGRAD and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
+        self.s2_wgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
                                  (ph, pw) == (1, 1) and Hi % 2 == 0 and Wi % 2 == 0 and Cout >= 64 and Cin >= 16 and
                                  N * Ho * Wo >= _NC8_S2_WGRAD_MIN_PIX)      # (the few-pixel encoder tails: one or two chunks per split, slabs dominate)
         # ... and the weight gradient of the 3x3 stride-1 pad-1 layers from the NC8 forms of X and dY (transposed LDS reads)
-        self.wgrad_nc8 = bool(self.nc8 and _NC8_WGRAD and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and
+        self.wgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and
                               (ph, pw) == (1, 1) and Cout >= 64 and Cin >= 16)      # (Cout = 32: half of a 64-row tile is padding -- 88 vs 145 TF/s on the NCHW kernel)
         if (kt, kh, kw) == (1, 3, 3) and (_patch_bf16_ok(Cin, stride, Ho, Wo, Cout, None, self.nc8) if bf16 else
                                           _patch_ok(Cin, (kt, kh, kw), stride, 1, Ho, Wo, Cout)):
@@ -1039,7 +1028,7 @@ class _ConvPlan:
         self.wg_geom[G.WGRAD_WIDE] = int(bf16 and sw == 1 and Wi == Wo and Wo % 8 == 0 and Wi >= 8 and kw in (1, 3)
                                and pw == (kw - 1) // 2 and osp % 8 == 0)
         # ... and its stride-2 form (4-wide taps, pad 1: dx = -1 .. 2; every second element of a 16-element run)
-        if bf16 and _WGRAD_WIDE_S2 and sw == 2 and Wi == 2 * Wo and Wo % 8 == 0 and kw == 4 and pw == 1 and osp % 8 == 0:
+        if bf16 and sw == 2 and Wi == 2 * Wo and Wo % 8 == 0 and kw == 4 and pw == 1 and osp % 8 == 0:
             self.wg_geom[G.WGRAD_WIDE] = 2
         self.wg_splits = L.c2m_conv_wgrad_splits(Cout, self.J, N * osp)
         # ---- dgrad: one launch per stride-parity class
@@ -1352,7 +1341,7 @@ def _packed(w, frozen, kind, build):
     if not frozen and w.is_cuda and torch.cuda.is_current_stream_capturing():
         # a pack that is kept fresh from outside the graph (refresh_trainable_packs after every optimizer step: same buffer,
         # new contents) is used as it is -- the graph then holds no pack kernels; pinned, because the graph keeps its address
-        if _PACK_REFRESH and fresh and key in _pack_jobs and _pack_jobs[key][3] is hit[3]:
+        if fresh and key in _pack_jobs and _pack_jobs[key][3] is hit[3]:
             _capture_pins[id(hit[3])] = hit[3]
             return hit[3]
         return build()
@@ -1362,7 +1351,7 @@ def _packed(w, frozen, kind, build):
     # optimizer): rebuild it IN PLACE.  A captured graph may hold the buffer's address (_capture_pins); a fresh allocation here
     # would leave that graph replaying the old weights for ever.
     job = _pack_jobs.get(key)
-    if _PACK_REFRESH and job is not None and hit is not None and job[0]() is w and hit[0]() is w and job[3] is hit[3] and \
+    if job is not None and hit is not None and job[0]() is w and hit[0]() is w and job[3] is hit[3] and \
             hit[2] == w.data_ptr():
         refresh_trainable_packs([w])
         return job[3]
@@ -1382,7 +1371,6 @@ def _packed(w, frozen, kind, build):
     return A
 
 
-_PACK_REFRESH = os.environ.get("C2M_PACK_REFRESH", "1") != "0"      # A/B knob: 0 = packs rebuilt lazily, one launch each
 _pack_jobs = {}          # (id(w), kind) -> (weakref(w), job type, g, packed tensor): packs of trainable weights we know how to rebuild
 _pack_tables = {}        # signature of a stale set -> (device job table, njobs, total workgroups)
 _capture_pins = {}       # id -> pack whose address a captured graph holds (one entry per pack, however many captures)
@@ -1393,7 +1381,7 @@ def refresh_trainable_packs(params=None):
     packed -- called by c2m_amd.optim.Adam.step and before a HIP-graph replay.  The packs keep their buffers, so the ~195 pack
     launches a full G + D step used to spend on its first use of every layer after the optimizer step (1.3 ms of GPU time, more
     host time than that) become one, and a captured graph needs no pack kernels at all.  Returns the number of packs rebuilt."""
-    if not _PACK_REFRESH or not _pack_jobs:
+    if not _pack_jobs:
         return 0
     stale = []
     if params is None:
@@ -2129,14 +2117,12 @@ class _NormActFn(torch.autograd.Function):
         invstd = torch.empty_like(mean)
         ws = torch.empty(L.c2m_norm_workspace_floats(N, C, S), device=x.device, dtype=torch.float32)
         y = torch.empty_like(x)
-        # bf16 data path: activations of conv-sized maps are ALSO written in the NC8 layout of the convolution they feed (and, in
-        # backward, the gradient they hand to the convolution in front): conv_nc8.hip then needs no layout pass of its own
-        ctx.nc8 = bool(_NC8 and _NC8_NORM and dt == 1 and x.dim() == 4 and S % 8 == 0 and C >= 16 and x.shape[3] >= 16 and S >= 512)
         # `feeds`: the result's only consumer is one convolution whose forward and weight gradient read NC8 -> NC8 is the ONLY output
+        # (writing both layouts measured slower than the layout passes it saved: 47.7 vs 47.05 ms, 71.5 vs 70.7 ms per bf16 step)
         only = False
         if feeds is not None and dt == 1 and S % 8 == 0:
             only = _consumer_reads_only_nc8(x, feeds)
-        yn = torch.empty((N, _cdiv(C, 8)) + tuple(x.shape[2:]) + (8,), device=x.device, dtype=BF16) if (ctx.nc8 or only) else None
+        yn = torch.empty((N, _cdiv(C, 8)) + tuple(x.shape[2:]) + (8,), device=x.device, dtype=BF16) if only else None
         if yn is None:
             # statistics + apply in one call: instance-norm planes of <= 32768 elements run as ONE launch (norm_inst_fused_kernel)
             _lib.check(L.c2m_norm_fwd_rep(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), _p(gamma), _p(beta), _p(gb),
@@ -2144,11 +2130,10 @@ class _NormActFn(torch.autograd.Function):
         else:
             _lib.check(L.c2m_norm_stats_rep(_p(x), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), N, C, S, mode,
                                             eps, momentum, rep, dt, _stream()), "norm_stats")
-            _lib.check(L.c2m_norm_apply(_p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(gb), None if only else _p(y), _p(yn), N, C, S,
+            _lib.check(L.c2m_norm_apply(_p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(gb), None, _p(yn), N, C, S,
                                         mode, ACT[act], LRELU_SLOPE, dt, _stream()), "norm_apply")
         if only and _NC8_POISON:
             y.fill_(float("nan"))
-        _NormActFn.last_only = only             # read by _norm_act right behind apply(): tags y as NC8-only
         ctx.cfg = (N, C, S, mode, act)
         # x is the output of a convolution whose backward reads its gradient in NC8 only, and this op is x's only consumer (the
         # caller's promise): dx is produced in NC8 form alone
@@ -2167,7 +2152,7 @@ class _NormActFn(torch.autograd.Function):
         gy = _as(gy, x.dtype)
         only = ctx.dx_nc8_only
         dx = torch.empty_like(x)
-        dxn = torch.empty((N, _cdiv(C, 8)) + tuple(x.shape[2:]) + (8,), device=x.device, dtype=BF16) if (ctx.nc8 or only) else None
+        dxn = torch.empty((N, _cdiv(C, 8)) + tuple(x.shape[2:]) + (8,), device=x.device, dtype=BF16) if only else None
         ggb = torch.empty_like(gb) if gb is not None else None
         dgamma = torch.empty_like(gamma) if gamma is not None else None
         dbeta = torch.empty_like(beta) if gamma is not None else None
@@ -2178,10 +2163,8 @@ class _NormActFn(torch.autograd.Function):
                    "norm_bwd")
         if only and _NC8_POISON:
             dx.fill_(float("nan"))
-        if dxn is not None and only:
+        if only:
             _mark_nc8_only(dx, dxn)               # autograd hands this very tensor object to the convolution's backward (see _to_nc8)
-        elif dxn is not None:
-            dx._c2m_nc8 = (dx._version, dxn)
         if ggb is not None and ggb.dtype != ctx.gb_dtype:
             ggb = ggb.to(ctx.gb_dtype)
         return dx, dgamma, dbeta, ggb, None, None, None, None, None, None, None, None, None
@@ -2189,10 +2172,8 @@ class _NormActFn(torch.autograd.Function):
 
 def _norm_act(*args, rep=1):
     y, yn = _NormActFn.apply(*args, rep)
-    if yn is not None and _NormActFn.last_only:
+    if yn is not None:                            # NC8 is the only output (`only` in _NormActFn.forward)
         _mark_nc8_only(y, yn)                     # y's NCHW storage was never written
-    elif yn is not None:
-        y._c2m_nc8 = (y._version, yn)             # the NC8 form travels with the tensor object (ops._to_nc8 picks it up)
     return y
 
 
@@ -2474,7 +2455,7 @@ class _GatDenseFn(torch.autograd.Function):
 
 
 GAT_DENSE_MAX_NODES, GAT_DENSE_MAX_CHANNELS = 64, 1024
-_GAT_FUSED = os.environ.get("C2M_GAT_FUSED", "1") != "0"
+_GAT_FUSED = True
 
 
 def gatv2_dense_ok(xl, N, C):

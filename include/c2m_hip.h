@@ -274,9 +274,9 @@ int c2m_norm_stats_rep(const void* x, float* mean, float* invstd, float* running
 int c2m_norm_fwd_rep(const void* x, float* mean, float* invstd, float* running_mean, float* running_var, float* workspace,
                      const float* gamma, const float* beta, const void* gb, void* y, int N, int C, long S, int mode, float eps,
                      float momentum, int rep, int act, float slope, int dt, void* stream);
-/* y_nc8 / dx_nc8 (optional; bf16 tensors with S % 8 == 0): the result ALSO in the channel-blocked layout [N][ceil(C/8)][S][8] the
- * NC8 convolutions consume (c2m_nchw_to_nc8's), written by the same pass -- the activation feeds a convolution, the gradient is the
- * dY of the convolution in front.                                                                                              */
+/* y_nc8 / dx_nc8 (bf16 tensors with S % 8 == 0): the result in the channel-blocked layout [N][ceil(C/8)][S][8] the NC8 convolutions
+ * consume (bit for bit c2m_nchw_to_nc8 of the NCHW result) INSTEAD of y / dx -- the activation feeds only a convolution, the gradient
+ * is the dY of the convolution in front.  Exactly one of (y, y_nc8) and of (dx, dx_nc8) is given: both return hipErrorInvalidValue. */
 int c2m_norm_apply(const void* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                    const void* gb, void* y, void* y_nc8, int N, int C, long S, int mode, int act, float slope, int dt, void* stream);
 int c2m_norm_bwd(const void* x, const void* gy, const float* mean, const float* invstd, const float* gamma,

@@ -109,12 +109,12 @@ def test_gather_nc8_splits_and_classes_are_exercised():
     assert all(seen.values()), seen
 
 
-@pytest.mark.parametrize("variant", [1, 2, 3, 4, 5, 6, 7])
+@pytest.mark.parametrize("variant", [1, 3, 5])
 def test_gather_nc8_tile_variants(variant):
     """Every (rows, K-steps per stage, stages) instantiation on a stride-2 layer with ragged rows and a ragged pixel tile."""
     ops._G8_VARIANT = variant
     ops._geom_cache.clear()
-    Cout = 24 if variant in (1, 7) else 168
+    Cout = 24 if variant == 1 else 168        # 32-row tiles serve <= 32 rows; 168 rows: ragged 128-row (3) and 64-row (5) tiles
     case = ((3, 40, 12, 16), Cout, (1, 4, 4), (1, 2, 2), (0, 1, 1), "reflect")
     pl, y, yr, xg, xr, wg, wr, bg, br = _run_case(case)
     assert pl.g8_fwd and pl.g8_dgrad and int(pl.g8_fwd_geom[ops.G.G8_VARIANT]) == variant

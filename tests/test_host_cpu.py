@@ -356,3 +356,23 @@ def test_build_sources_exist_and_every_included_header_is_tracked(monkeypatch):
         assert os.path.realpath(os.path.join(c2m_build.CSRC, src)) in tracked, src
         missing = quoted(os.path.join(c2m_build.CSRC, src), set()) - tracked
         assert not missing, f"{src} includes headers build() does not track: {sorted(missing)}"
+
+
+def test_environment_variables_are_the_documented_table():
+    """Every C2M_* variable c2m_amd/ reads -- os.environ in the Python files, getenv in csrc/ -- is a row of the table in
+    INTEGRATION.md §3, and every row is read somewhere: a new knob comes with its documentation, a retired one leaves the table."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    name = r"(C2M_[A-Z0-9_]+)"
+    read = set()
+    for dirpath, _, files in os.walk(os.path.join(root, "c2m_amd")):
+        for f in files:
+            text = open(os.path.join(dirpath, f), errors="replace").read() if f.endswith((".py", ".hip", ".h")) else ""
+            if f.endswith(".py"):
+                read |= set(re.findall(r"os\.environ(?:\.get\(|\.pop\(|\.setdefault\(|\[)\s*[\"']" + name + "[\"']", text))
+                read |= set(re.findall("[\"']" + name + r"[\"']\s+(?:not\s+)?in\s+os\.environ", text))
+            elif os.path.basename(dirpath) == "csrc":
+                read |= set(re.findall(r"getenv\(\s*\"" + name + "\"", text))
+    table = set(re.findall(r"^\| `" + name + r"` \|", open(os.path.join(root, "INTEGRATION.md")).read(), re.M))
+    assert len(table) >= 10, "the table of environment variables in INTEGRATION.md was not found"
+    assert read == table, f"read but not documented: {sorted(read - table)}; documented but not read: {sorted(table - read)}"

@@ -1,6 +1,6 @@
 """bf16 layers outside the NC8 patch forms: the NCHW 2-byte-gather kernel (C2M_G8=0 rule) against the NC8 gather form
-(conv_gather_nc8_kernel) on bench shapes of configs[2-4]; forward and data gradient per tile variant, results compared.
-    python tools/ab_g8.py [iters]        AB_VARIANTS=0,2,5 picks the variants (0 = the rule)"""
+(conv_gather_nc8_kernel) on bench shapes of configs[2-4]; forward and data gradient, results compared.
+    python tools/ab_g8.py [iters]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -53,14 +53,11 @@ def run(g8, xs, Cout, k, stride, pad, mode):
     return y.detach(), x.grad.clone(), {k_: ((v[0], v[1] / (v[0] * iters / 1000)) if isinstance(v, list) else v) for k_, v in tab.items()}
 
 
-VARIANTS = [int(v) for v in os.environ.get("AB_VARIANTS", "0").split(",")]
 for shp in SHAPES:
     y0, g0, t0 = run(False, *shp)
     msg = f"{str(shp):62s} old fwd {t0['fwd'][0]:6.1f} us {t0['fwd'][1]:4.0f} TF/s (S {t0['Sfwd']}) dgrad {t0['dgrad'][0]:6.1f} us {t0['dgrad'][1]:4.0f} (S {t0['Sdgrad']})"
-    for v in VARIANTS:
-        ops._G8_VARIANT = v
-        y1, g1, t1 = run(True, *shp)
-        ey = float((y1.float() - y0.float()).abs().max() / y0.float().abs().max())
-        eg = float((g1.float() - g0.float()).abs().max() / g0.float().abs().max())
-        msg += f" | v{v}: fwd {t1['fwd'][0]:6.1f} us {t1['fwd'][1]:4.0f} (S {t1['Sfwd']}) dgrad {t1['dgrad'][0]:6.1f} us {t1['dgrad'][1]:4.0f} (S {t1['Sdgrad']}) diff {ey:.0e} {eg:.0e}"
+    y1, g1, t1 = run(True, *shp)
+    ey = float((y1.float() - y0.float()).abs().max() / y0.float().abs().max())
+    eg = float((g1.float() - g0.float()).abs().max() / g0.float().abs().max())
+    msg += f" | g8: fwd {t1['fwd'][0]:6.1f} us {t1['fwd'][1]:4.0f} (S {t1['Sfwd']}) dgrad {t1['dgrad'][0]:6.1f} us {t1['dgrad'][1]:4.0f} (S {t1['Sdgrad']}) diff {ey:.0e} {eg:.0e}"
     print(msg, flush=True)
