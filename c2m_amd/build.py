@@ -23,7 +23,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_gather.hip": NOSLP, "conv_patch.hip": 
            "resize.hip": ["-ffp-contract=off"] + NOSLP,
            "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "nearest_fill.hip": ["-ffp-contract=off"] + NOSLP,
-           "dense_flow.hip": ["-ffp-contract=off"] + NOSLP,
+           "dense_flow.hip": ["-ffp-contract=off"] + NOSLP, "flow_refine.hip": ["-ffp-contract=off"] + NOSLP,
            "detail_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
@@ -47,7 +47,7 @@ def build(force=False, verbose=False, variant=None, defines=()):
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [os.path.join(CSRC, h) for h in ("common.h", "wave.h", "instance_compact.h", "dtype.h", "conv_store.h", "conv_types.h", "conv_common.h",
-                                              "warp_coord.h")] + \
+                                              "warp_coord.h", "flow_sample.h")] + \
         [os.path.join(os.path.dirname(HERE), "include", h) for h in ("c2m_geom.h", "c2m_hip.h")]   # common.h includes both
     suffix = f"_{variant}" if variant else ""
     lib = LIB.replace(".so", suffix + ".so")

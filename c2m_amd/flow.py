@@ -7,9 +7,10 @@ last input frame) and is read by `ops.label_warp` and `tracking.track_instances`
 it drops into `train.compute_flow`, into `tracking.tracked_batch`'s inputs and into `interactive.rollout(flow_fn=...)`.
 
 The algorithm is a coarse-to-fine inverse search over 8 x 8 patches at stride 4 (one wave64 per patch), a fixed number of steps
-per patch and a weighted average of the patches that cover a pixel.  There is NO variational refinement, and a motion of more
-than about 8 px at the coarsest level (25 px at 128 x 256, four levels) is out of range.  Nothing here has weights; nothing is
-differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
+per patch and a weighted average of the patches that cover a pixel.  `refine=True` adds a variational refinement of every level's
+flow (csrc/flow_refine.hip; off by default).  A motion of more than about 8 px at the coarsest level (25 px at
+128 x 256, four levels) is out of range.  Nothing here has weights; nothing is differentiated.  There is no CPU path: a tensor
+that is not on a HIP device raises.
 """
 import torch
 import torch.nn as nn
@@ -17,6 +18,8 @@ import torch.nn as nn
 from . import _lib, ops
 
 PATCH, STRIDE, MAX_LEVELS = 8, 4, 7
+REFINE_DEFAULTS = dict(alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6)      # OpenCV's DIS defaults; images on 0..255
+SOR_CAP = 5                                                   # the iterate kernel's tile has a halo of 2 * sor <= 10 pixels
 
 
 def pyramid_sizes(H, W, levels=None):
@@ -130,14 +133,101 @@ def densify(ia, ib, records, shift=0, out_size=None, out=None):
     return flow
 
 
-def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12):
+def refine_params(refine):
+    """None / False -> None (no refinement); True -> REFINE_DEFAULTS; a dict overrides them, an unknown key raises.  The values
+    are checked here, on the host: outer >= 1, 1 <= sor <= SOR_CAP, 0 < omega < 2, alpha, delta, gamma > 0."""
+    if refine is None or refine is False:
+        return None
+    p = dict(REFINE_DEFAULTS)
+    if refine is not True:
+        if not isinstance(refine, dict):
+            raise ValueError(f"refine must be None, a bool or a dict of {sorted(p)}, got {type(refine).__name__}")
+        unknown = sorted(set(refine) - set(p))
+        if unknown:
+            raise ValueError(f"refine: unknown parameters {unknown} (known: {sorted(p)})")
+        p.update(refine)
+    for k in ("alpha", "delta", "gamma"):
+        p[k] = float(p[k])
+        if not 0 < p[k] < float("inf"):
+            raise ValueError(f"refine: {k} must be a positive weight, got {p[k]}")
+    p["omega"], p["outer"], p["sor"] = float(p["omega"]), int(p["outer"]), int(p["sor"])
+    if not 0 < p["omega"] < 2:
+        raise ValueError(f"refine: omega must be in (0, 2), got {p['omega']}")
+    if not 1 <= p["outer"] <= 1024:
+        raise ValueError(f"refine: outer must be 1 .. 1024, got {p['outer']}")
+    if not 1 <= p["sor"] <= SOR_CAP:
+        raise ValueError(f"refine: sor must be 1 .. {SOR_CAP} (the halo of the iterate kernel's tile), got {p['sor']}")
+    return p
+
+
+def _refine_workspace(N, h, w, device):
+    nbytes = _lib.lib().c2m_flow_refine_workspace_bytes(N, h, w)
+    if nbytes < 0:
+        raise ValueError(f"refine_flow: sizes out of range (N={N}, h={h}, w={w})")
+    return torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+
+
+def _level_inputs(ia, ib, flow):
+    """The checks of a level's images and its dense flow [N,2,h,w]."""
+    ia, ib = _level_images(ia, ib)
+    N, h, w = ia.shape
+    if not isinstance(flow, torch.Tensor) or flow.dtype != torch.float32 or tuple(flow.shape) != (N, 2, h, w):
+        raise ValueError(f"flow must be fp32 {[N, 2, h, w]}, got {list(getattr(flow, 'shape', ()))}")
+    ops._hip_only(flow)
+    return ia, ib, flow.detach().contiguous()
+
+
+def refine_planes(ia, ib, flow, work=None):
+    """The eight planes (Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz) [8,N,h,w] of one level (a view of the workspace), ONE launch."""
+    ia, ib, flow = _level_inputs(ia, ib, flow)
+    N, h, w = ia.shape
+    work = _refine_workspace(N, h, w, ia.device) if work is None else work
+    _lib.check(_lib.lib().c2m_flow_refine_prepare(ops._p(ia), ops._p(ib), ia.numel(), ops._p(flow), flow.numel(), ops._p(work),
+                                                  work.numel() * 4, N, h, w, ops._stream()), "flow_refine_prepare")
+    return work[:8 * N * h * w].view(8, N, h, w)
+
+
+def _refine_level(ia, ib, flow, p, work, out, shift=0):
+    """prepare + p['outer'] iterate launches; flow [N,2,h,w] contiguous; the last iteration writes `out` [N,2,Ho,Wo]."""
+    N, h, w = ia.shape
+    refine_planes(ia, ib, flow, work)
+    L, nbytes = _lib.lib(), work.numel() * 4
+    for k in range(p["outer"]):
+        last = k == p["outer"] - 1
+        _lib.check(L.c2m_flow_refine_iterate(ops._p(flow), flow.numel(), ops._p(work), nbytes, N, h, w, k, p["sor"], p["alpha"],
+                                             p["delta"], p["gamma"], p["omega"], ops._p(out) if last else None,
+                                             out.numel() if last else 0, int(shift), out.shape[2], out.shape[3], ops._stream()),
+                   "flow_refine_iterate")
+    return out
+
+
+def refine_flow(ia, ib, flow, alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6, out=None):
+    """Variational refinement of one level: ia, ib [N,h,w] fp32 gray on 0..255 and the level's dense flow
+    [N,2,h,w] -> the refined flow [N,2,h,w].  `outer` fixed-point iterations of `sor` (<= SOR_CAP) red-black SOR sweeps with
+    relaxation omega; alpha, delta, gamma weigh smoothness, brightness and gradient constancy.  1 + outer launches on the
+    current stream, no synchronisation; bit-repeatable and independent of N."""
+    p = refine_params(dict(alpha=alpha, delta=delta, gamma=gamma, outer=outer, sor=sor, omega=omega))
+    ia, ib, flow = _level_inputs(ia, ib, flow)
+    N, h, w = ia.shape
+    if out is None:
+        out = torch.empty_like(flow)
+    elif out.data_ptr() == flow.data_ptr():
+        raise ValueError("refine_flow: out must not be the input flow (a tile reads its neighbours' input)")
+    return _refine_level(ia, ib, flow, p, _refine_workspace(N, h, w, ia.device), out)
+
+
+def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine=None):
     """Flow a -> b of N image pairs -> [N,2,H,W] fp32 pixels (channel 0 = x; a(x) ~ b(x + flow(x))).
 
     a, b [N,3,H,W] fp32 or bf16 on the device, H, W >= 8, values in value_range = (lo, hi).  levels: at most that many pyramid
     levels (by default levels are added while min(h, w) // 2 >= 16).  finest: the last level searched; its flow is brought to
     level 0 by 2 * f[y // 2, x // 2] per level.  iters: search steps per patch and level, the same for every patch.
-    1 + 2 * (levels - finest) launches on the current stream whatever N is, no synchronisation, no copy to the host; the result
-    is bit-repeatable and that of a pair does not depend on the other pairs of the call.  No gradient flows through it."""
+    refine: None / False: the densified patch flow; True: the variational refinement of DESIGN.md 4.2m after the densify of
+    every searched level, with REFINE_DEFAULTS; a dict overrides those (see refine_params).
+    1 + 2 * (levels - finest) launches on the current stream whatever N is (1 + (3 + outer) * (levels - finest) with refinement),
+    no synchronisation, no copy to the host; the result is bit-repeatable and that of a pair does not depend on the other pairs
+    of the call.  No gradient flows through it."""
+    rp = refine_params(refine)
     with torch.no_grad():
         work, sizes, images = flow_pyramid(a, b, value_range, levels)
         N, (H, W), n = a.shape[0], sizes[0], len(sizes)
@@ -150,10 +240,20 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12):
         rec0 = L.c2m_flow_workspace_offset(N, H, W, n, 3, 0)
         out = torch.empty(N, 2, H, W, device=a.device, dtype=torch.float32)
         flow = None
+        if rp is not None:                                            # the refinement's own buffers, sized for the finest level
+            hf, wf = sizes[finest]
+            rwork, patchflow = _refine_workspace(N, hf, wf, a.device), torch.empty(2 * N * hf * wf, device=a.device)
         for l in range(n - 1, finest - 1, -1):
             (h, w), (ia, ib) = sizes[l], images[l]
             npy, npx = len(patch_origins(h)), len(patch_origins(w))
             rec = patch_search(ia, ib, flow, iters, out=work[rec0:rec0 + N * npy * npx * 3].view(N, npy, npx, 3))
+            if rp is not None:                                        # densify -> refine -> the place the plain flow would go to
+                dense = densify(ia, ib, rec, out=patchflow[:2 * N * h * w].view(N, 2, h, w))
+                if l == finest:
+                    return _refine_level(ia, ib, dense, rp, rwork, out, shift=l)
+                o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)
+                flow = _refine_level(ia, ib, dense, rp, rwork, work[o:o + 2 * N * h * w].view(N, 2, h, w))
+                continue
             if l == finest:
                 return densify(ia, ib, rec, shift=l, out_size=(H, W), out=out)
             o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)
@@ -164,11 +264,13 @@ class ClassicFlow(nn.Module):
     """dense_flow behind FlowNet's call surface: `flow, conf = ClassicFlow()(A, B)` for 4-D [N,3,H,W], 5-D [b,n,3,H,W] and 6-D
     [b,t,n,3,H,W] inputs, with conf = ops.occlusion_splat(flow)[0] as FlowNet computes it.  value_range defaults to (-1, 1),
     where train.compute_flow puts the frames; ClassicFlow(value_range=(0, 1)).compute_flow_and_conf is the `flow_fn` of
-    interactive.rollout.  No weights, no resize to multiples of 64: any size >= 8."""
+    interactive.rollout.  refine: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8."""
 
-    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12):
+    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None):
         super().__init__()
         self.value_range, self.levels, self.finest, self.iters = tuple(value_range), levels, finest, iters
+        refine_params(refine)                                         # a bad parameter raises here, not at the first call
+        self.refine = refine
 
     def forward(self, input_A, input_B):
         size = input_A.size()
@@ -181,7 +283,7 @@ class ClassicFlow(nn.Module):
         return flow.view(*size[:-3], 2, h, w), conf.view(*size[:-3], 1, h, w)
 
     def compute_flow_and_conf(self, im1, im2):
-        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters)
+        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters, self.refine)
         with torch.no_grad():
             conf = ops.occlusion_splat(flow)[0]
         return flow, conf

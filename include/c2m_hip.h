@@ -412,6 +412,27 @@ int c2m_flow_patch_search(const float* ia, const float* ib, long image_elems, co
 int c2m_flow_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
                      float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, void* stream);
 
+/* ---- variational refinement of the dense flow (flow_refine.hip): c2m_amd.flow.refine_flow, dense_flow(refine=...) ----------
+ * The reference has no counterpart.  On ONE pyramid level: ia, ib [N][h][w] gray on 0..255 (image_elems floats each), flow
+ * [N][2][h][w] the level's dense flow (u, v); 8 <= h, w <= 32768.  DESIGN.md 4.2m states every formula and its association order.
+ * c2m_flow_refine_workspace_bytes: the workspace of one level (-1 for sizes out of range), 4-byte aligned, never zeroed: the
+ *   planes Ix, Iy, Iz, Ixx, Ixy, Iyy, Ixz, Iyz as [8][N][h][w], then (du, dv) [N][2][h][w] twice.
+ * c2m_flow_refine_prepare: the eight planes from ia, ib and flow, ONE launch (J = ib sampled at x + flow, the coordinate clamped
+ *   to the image before the gather; central differences with clamped indices).
+ * c2m_flow_refine_iterate: outer iteration `iteration` (0, 1, ...; < 1024), ONE launch: the weights and the linear system from
+ *   (du, dv) of iteration - 1 (zero for iteration 0), then `sor` (1 .. 5) red-black SOR sweeps with relaxation omega (0 .. 2),
+ *   colour (x + y) & 1 == 0 first; alpha, delta, gamma > 0.  out NULL: (du, dv) goes to the workspace, to the copy of index
+ *   iteration & 1.  out [N][2][Ho][Wo] (the last iteration): pixel (Y, X) = 2^shift * (u + du, v + dv) at level pixel
+ *   (Y >> shift, X >> shift), shift 0 .. 6, ((Ho - 1) >> shift) < h; out must not be `flow`.
+ * Every size, extent and parameter is checked before the launch; both run on `stream`; no atomics, no synchronisation, no host
+ * copy: bit-repeatable, independent of N and of the tiling (equal to the global red-black sweep in fp32).                       */
+long c2m_flow_refine_workspace_bytes(int N, int h, int w);
+int c2m_flow_refine_prepare(const float* ia, const float* ib, long image_elems, const float* flow, long flow_elems,
+                            void* workspace, long workspace_bytes, int N, int h, int w, void* stream);
+int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h, int w,
+                            int iteration, int sor, float alpha, float delta, float gamma, float omega, float* out,
+                            long out_elems, int shift, int Ho, int Wo, void* stream);
+
 /* ---- predicted frames at dataset resolution (detail_warp.hip): c2m_amd.fullres ---------------------------------------------
  * The reference has no counterpart.  frame [B][H][W][3] uint8 is the last input frame at the output size; generated, warped
  * [B][3][T][h][w], flow [B][2][T][h][w] (working-size pixels) and occ [B][1][T][h][w] (NULL: 1 everywhere) are dense fp32 at the

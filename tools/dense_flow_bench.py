@@ -7,8 +7,8 @@ The 96 pairs at 128 x 256 are those of a B = 8 step with 2 input and 5 predicted
 1/f texture and the same texture moved by a smooth flow of a few pixels, so the search runs on real structure (its cost does not
 depend on the data: every patch does the same number of steps).  The two are timed alternately in one process after --warmup
 rounds, HIP events around each call; median, minimum and maximum of --iters repetitions.  `dense_flow` is the flow alone,
-`classic` adds the occlusion map (ops.occlusion_splat) as ClassicFlow returns it, `flownet2` is FlowNet(pretrained=False)(A, B),
-which also includes that map.  Prints one JSON line; --out appends it to a file.  A tool, not a test: it carries no threshold."""
+`dense_flow_refined` the same with the variational refinement (refine=True; csrc/flow_refine.hip), `classic` adds the occlusion
+map (ops.occlusion_splat) as ClassicFlow returns it, `flownet2` is FlowNet(pretrained=False)(A, B), which also includes that map.  Prints one JSON line; --out appends it to a file.  A tool, not a test: it carries no threshold."""
 import argparse
 import json
 import os
@@ -69,11 +69,18 @@ def main():
     flow = F.dense_flow(A, B, value_range=(-1, 1))
     inner = (slice(None), slice(None), slice(16, H - 16), slice(16, W - 16))
     err = (flow - torch.tensor([3.0, -2.0], device=flow.device).view(1, 2, 1, 1))[inner].square().sum(1).sqrt().mean()
-    fns = [lambda: F.dense_flow(A, B, value_range=(-1, 1)), lambda: classic(A, B), lambda: net(A, B)]
-    t_flow, t_classic, t_net = timed(fns, a.iters, a.warmup)
+    refined = F.dense_flow(A, B, value_range=(-1, 1), refine=True)
+    err_refined = (refined - torch.tensor([3.0, -2.0], device=flow.device).view(1, 2, 1, 1))[inner].square().sum(1).sqrt().mean()
+    fns = [lambda: F.dense_flow(A, B, value_range=(-1, 1)), lambda: F.dense_flow(A, B, value_range=(-1, 1), refine=True),
+           lambda: classic(A, B), lambda: net(A, B)]
+    t_flow, t_refined, t_classic, t_net = timed(fns, a.iters, a.warmup)
+    levels, rp = len(F.pyramid_sizes(H, W)), F.REFINE_DEFAULTS
     res = {"pairs": a.pairs, "size": [H, W], "levels": len(F.pyramid_sizes(H, W)), "iters": a.iters,
            "launches_dense_flow": 1 + 2 * len(F.pyramid_sizes(H, W)), "mean_epe_px_16px_from_border": round(float(err), 4),
-           "dense_flow": t_flow, "classic": t_classic, "flownet2": t_net,
+           "launches_dense_flow_refined": 1 + (3 + rp["outer"]) * levels,
+           "mean_epe_px_16px_from_border_refined": round(float(err_refined), 4),
+           "dense_flow": t_flow, "dense_flow_refined": t_refined,
+           "refined_over_plain": round(t_refined["median_ms"] / t_flow["median_ms"], 1), "classic": t_classic, "flownet2": t_net,
            "flownet2_over_classic": round(t_net["median_ms"] / t_classic["median_ms"], 1)}
     line = json.dumps(res)
     print(line, flush=True)
