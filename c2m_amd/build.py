@@ -24,6 +24,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_gather.hip": NOSLP, "conv_patch.hip": 
            "warp.hip": ["-ffp-contract=off"] + NOSLP, "label_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "nearest_fill.hip": ["-ffp-contract=off"] + NOSLP,
            "dense_flow.hip": ["-ffp-contract=off"] + NOSLP, "flow_refine.hip": ["-ffp-contract=off"] + NOSLP,
+           "flow_chain.hip": ["-ffp-contract=off"] + NOSLP,
            "detail_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,

@@ -9,8 +9,9 @@ it drops into `train.compute_flow`, into `tracking.tracked_batch`'s inputs and i
 The algorithm is a coarse-to-fine inverse search over 8 x 8 patches at stride 4 (one wave64 per patch), a fixed number of steps
 per patch and a weighted average of the patches that cover a pixel.  `refine=True` adds a variational refinement of every level's
 flow (csrc/flow_refine.hip; off by default).  A motion of more than about 8 px at the coarsest level (25 px at
-128 x 256, four levels) is out of range.  Nothing here has weights; nothing is differentiated.  There is no CPU path: a tensor
-that is not on a HIP device raises.
+128 x 256, four levels) is out of range of ONE search; frames of a clip that are further apart get their flow from the flows
+between consecutive frames, chained (`chain_flows`, `clip_flows`, `ClassicFlow(chain=True)`; csrc/flow_chain.hip; DESIGN.md
+4.2n).  Nothing here has weights; nothing is differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
 """
 import torch
 import torch.nn as nn
@@ -20,6 +21,7 @@ from . import _lib, ops
 PATCH, STRIDE, MAX_LEVELS = 8, 4, 7
 REFINE_DEFAULTS = dict(alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6)      # OpenCV's DIS defaults; images on 0..255
 SOR_CAP = 5                                                   # the iterate kernel's tile has a halo of 2 * sor <= 10 pixels
+CHAIN_CAP = 16                                                # the most steps one chain_flows call follows
 
 
 def pyramid_sizes(H, W, levels=None):
@@ -260,17 +262,87 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine
             flow = densify(ia, ib, rec, out=work[o:o + 2 * N * h * w].view(N, 2, h, w))
 
 
+def chain_flows(steps, order="backward", return_valid=False):
+    """The flows across 1 .. K frames of N clips from the K flows between consecutive frames: steps
+    [N,K,2,H,W] fp32 on the device -> [N,K,2,H,W].  Frames c_0 .. c_K.  order "backward": steps[:, j] is the flow c_{j+1} -> c_j
+    and out[:, k] the flow c_{k+1} -> c_0; "forward": steps[:, j] is c_j -> c_{j+1} and out[:, k] is c_0 -> c_{k+1}.  Every pixel
+    is followed through the steps: its displacement d starts at 0 and each hop adds the step sampled at pixel + d (bilinear,
+    the coordinate clamped to the frame for the read only).  out[:, 0] is steps[:, 0].  return_valid: also a uint8 [N,K,H,W],
+    1 where pixel + d stayed inside the frame after every hop.  1 <= K <= CHAIN_CAP.  ONE launch on the current stream
+    whatever N and K are, no synchronisation; bit-repeatable, and the result of a clip does not depend on the others."""
+    if order not in ("backward", "forward"):
+        raise ValueError(f"order must be 'backward' or 'forward', got {order!r}")
+    if not isinstance(steps, torch.Tensor) or steps.dim() != 5 or steps.shape[2] != 2 or steps.dtype != torch.float32:
+        raise ValueError(f"steps must be a fp32 [N,K,2,H,W] tensor, got {getattr(steps, 'dtype', None)} "
+                         f"{list(getattr(steps, 'shape', ()))}")
+    N, K, _, H, W = steps.shape
+    if not 1 <= K <= CHAIN_CAP or H < 1 or W < 1:
+        raise ValueError(f"chain_flows needs 1 <= K <= {CHAIN_CAP} and H, W >= 1, got K={K}, H={H}, W={W}")
+    if steps.numel() >= 1 << 31:
+        raise ValueError(f"chain_flows: N * K * 2 * H * W must be below 2^31, got {steps.numel()}")
+    ops._hip_only(steps)
+    ops._on_current_device(steps)
+    with torch.no_grad():
+        steps = steps.detach().contiguous()
+        out = torch.empty_like(steps)
+        valid = torch.empty(N, K, H, W, device=steps.device, dtype=torch.uint8) if return_valid else None
+        _lib.check(_lib.lib().c2m_flow_chain(ops._p(steps), steps.numel(), ops._p(out), out.numel(), ops._p(valid),
+                                             0 if valid is None else valid.numel(), N, K, H, W, int(order == "forward"),
+                                             ops._stream()), "flow_chain")
+    return (out, valid) if return_valid else out
+
+
+def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, value_range=(0, 1), **dense_flow_kw):
+    """The dict of train.compute_flow for video [B,3,T,H,W] (T >= t_in + t_out; values in value_range), with the flows between
+    the last input frame and the predicted frames CHAINED through the frames in between instead of searched across up to t_out
+    frames: `target_bw_of` [B,2,t_out,H,W] is the backward chain from the last input frame, `target_bw_occ` [B,1,t_out,H,W] is
+    ops.occlusion_splat of the forward chain; with use_fw_of, `target_fw_of` is the forward chain and `target_fw_occ` the map of
+    the backward one.  `input_of` / `input_occ` (None for t_in = 1) are the consecutive flows themselves, as compute_flow has
+    them, and so is the first target frame.  ONE dense_flow call over the 2 (t_in - 1 + t_out) B consecutive pairs (both
+    directions; dense_flow_kw: levels, finest, iters, refine), two chain launches, the splats and the copies that bring the
+    results into compute_flow's layout: a number of launches that does not depend on B."""
+    t_in, t_out = int(num_input_frames), int(num_predicted_frames)
+    if t_in < 1 or not 1 <= t_out <= CHAIN_CAP:
+        raise ValueError(f"clip_flows needs num_input_frames >= 1 and 1 <= num_predicted_frames <= {CHAIN_CAP}, got {t_in}, {t_out}")
+    if not isinstance(video, torch.Tensor) or video.dim() != 5 or video.shape[1] != 3 or video.shape[2] < t_in + t_out:
+        raise ValueError(f"video must be a [B,3,T,H,W] tensor with T >= {t_in + t_out}, got {list(getattr(video, 'shape', ()))}")
+    B, _, _, H, W = video.shape
+    n, n_in = t_in + t_out - 1, t_in - 1                              # consecutive pairs of a clip; those between input frames
+    with torch.no_grad():
+        frames = video.detach()[:, :, :n + 1].transpose(1, 2)         # [B,T,3,H,W]
+        f0, f1 = frames[:, :-1].reshape(B * n, 3, H, W), frames[:, 1:].reshape(B * n, 3, H, W)
+        flows = dense_flow(torch.cat([f0, f1]), torch.cat([f1, f0]), value_range, **dense_flow_kw).view(2, B, n, 2, H, W)
+        fw, bw = flows[0], flows[1]                                   # [:, j]: c_j -> c_{j+1} and c_{j+1} -> c_j
+        fw_chain, bw_chain = chain_flows(fw[:, n_in:], "forward"), chain_flows(bw[:, n_in:], "backward")
+        layout = lambda f: f.transpose(1, 2).contiguous()             # [B,K,2,H,W] -> [B,2,K,H,W]
+        out = {"input_of": layout(fw[:, :n_in]) if n_in else None,
+               "input_occ": ops.occlusion_splat(layout(bw[:, :n_in]))[0] if n_in else None}
+        fw_chain, bw_chain = layout(fw_chain), layout(bw_chain)
+        out["target_bw_of"], out["target_bw_occ"] = bw_chain, ops.occlusion_splat(fw_chain)[0]
+        if use_fw_of:
+            out["target_fw_of"], out["target_fw_occ"] = fw_chain, ops.occlusion_splat(bw_chain)[0]
+    return out
+
+
 class ClassicFlow(nn.Module):
     """dense_flow behind FlowNet's call surface: `flow, conf = ClassicFlow()(A, B)` for 4-D [N,3,H,W], 5-D [b,n,3,H,W] and 6-D
     [b,t,n,3,H,W] inputs, with conf = ops.occlusion_splat(flow)[0] as FlowNet computes it.  value_range defaults to (-1, 1),
     where train.compute_flow puts the frames; ClassicFlow(value_range=(0, 1)).compute_flow_and_conf is the `flow_fn` of
-    interactive.rollout.  refine: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8."""
+    interactive.rollout.  refine: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8.
+    chain=True: train.compute_flow takes its targets from `clip_flows` (the consecutive flows of the clip, chained) instead of
+    searching each (last input frame, predicted frame) pair directly; the call surface above is the same either way."""
 
-    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None):
+    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None, chain=False):
         super().__init__()
         self.value_range, self.levels, self.finest, self.iters = tuple(value_range), levels, finest, iters
         refine_params(refine)                                         # a bad parameter raises here, not at the first call
-        self.refine = refine
+        self.refine, self.chain = refine, bool(chain)
+
+    def clip_flows(self, train_batch, train_params):
+        """train.compute_flow's dict for a batch, by `clip_flows`; the frames go to [-1, 1] first, as compute_flow puts them."""
+        return clip_flows(train_batch["video"] * 2 - 1, train_params["num_input_frames"], train_params["num_predicted_frames"],
+                          train_params.get("use_fw_of", False), self.value_range, levels=self.levels, finest=self.finest,
+                          iters=self.iters, refine=self.refine)
 
     def forward(self, input_A, input_B):
         size = input_A.size()

@@ -34,7 +34,11 @@ def compute_flow(flownet, train_batch, train_params):
     occlusion comes from the reverse pair); between the last input frame and every predicted frame both directions ->
     `target_bw_of` / `target_bw_occ` (and `target_fw_*` when `use_fw_of`).  Frames are mapped to [-1, 1] first.
     The 2 * (t_in - 1 + t_out) flow-net passes of the reference loop are issued as ONE batched pass: the pairs are
-    independent images and every kernel of the net is batch-wise bit-deterministic."""
+    independent images and every kernel of the net is batch-wise bit-deterministic.
+    A flow module with a true `chain` attribute (flow.ClassicFlow(chain=True)) returns the same dict from its own `clip_flows`:
+    the flows between consecutive frames, chained across the gap."""
+    if getattr(flownet, "chain", False):
+        return flownet.clip_flows(train_batch, train_params)
     t_in, t_out = train_params["num_input_frames"], train_params["num_predicted_frames"]
     video = train_batch["video"]
     b = video.shape[0]

@@ -433,6 +433,21 @@ int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* workspace,
                             int iteration, int sor, float alpha, float delta, float gamma, float omega, float* out,
                             long out_elems, int shift, int Ho, int Wo, void* stream);
 
+/* ---- chains of frame-to-frame flows (flow_chain.hip): c2m_amd.flow.chain_flows, clip_flows ---------------------------------
+ * The reference has no counterpart.  Frames c_0 .. c_K of N clips; steps [N][K][2][H][W] fp32, channel 0 = x, pixels, with the
+ * convention above; out [N][K][2][H][W]; valid [N][K][H][W] uint8 or NULL.  DESIGN.md 4.2n states the algorithm.
+ * forward 0: steps[j] is the flow c_{j+1} -> c_j and out[k] the flow c_{k+1} -> c_0: from every pixel of c_{k+1}, d = (0, 0),
+ *   then for j = k .. 0: d += steps[j] sampled at pixel + d.  forward 1: steps[j] is c_j -> c_{j+1}, out[k] is c_0 -> c_{k+1}:
+ *   one walk j = 0 .. K - 1 from every pixel of c_0 that writes d after every hop.  The sample is the bilinear gather of the
+ *   flow kernels: its coordinate is clamped to the image first (a NaN goes to 0), so every read is inside the step planes
+ *   whatever they hold; pixel + d itself is never clamped.  The first hop reads at integer coordinates with weight 1: out[0]
+ *   is steps[0] for finite steps.  valid is 1 iff pixel + d was inside [0, W - 1] x [0, H - 1] after every hop (a NaN: 0).
+ * 1 <= K <= 16, H, W >= 1, N * K * 2 * H * W < 2^31; step_elems, out_elems >= N * K * 2 * H * W, valid_elems >= N * K * H * W;
+ * out must not be steps.  Everything is checked before the launch; ONE launch on `stream`, no atomics, no synchronisation, no
+ * host copy: bit-repeatable, and the result of a clip does not depend on N.                                                    */
+int c2m_flow_chain(const float* steps, long step_elems, float* out, long out_elems, uint8_t* valid, long valid_elems,
+                   int N, int K, int H, int W, int forward, void* stream);
+
 /* ---- predicted frames at dataset resolution (detail_warp.hip): c2m_amd.fullres ---------------------------------------------
  * The reference has no counterpart.  frame [B][H][W][3] uint8 is the last input frame at the output size; generated, warped
  * [B][3][T][h][w], flow [B][2][T][h][w] (working-size pixels) and occ [B][1][T][h][w] (NULL: 1 everywhere) are dense fp32 at the
