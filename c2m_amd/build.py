@@ -29,6 +29,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_gather.hip": NOSLP, "conv_patch.hip": 
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
            "panoptic.hip": ["-ffp-contract=off"] + NOSLP,
+           "components.hip": NOSLP,                      # integer kernels: nothing to contract
            "map_quality.hip": ["-ffp-contract=off"] + NOSLP,
            "motion_raster.hip": ["-ffp-contract=off"] + NOSLP, "events.hip": [],
            "render.hip": ["-ffp-contract=off"] + NOSLP, "detect.hip": ["-ffp-contract=off"] + NOSLP,

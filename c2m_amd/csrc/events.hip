@@ -25,6 +25,20 @@ C2M_API int c2m_event_destroy(void* ev) {
     return (int)hipEventDestroy((hipEvent_t)ev);
 }
 
+// ---- graph capture, for the tests: the number of nodes the capture on `stream` has recorded so far (0 when it is not capturing).
+// The difference around a call is the number of launches (and memset / copy nodes) the call put on the stream.
+C2M_API int c2m_capture_node_count(void* stream, long* nodes) {
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    hipGraph_t graph = nullptr;
+    *nodes = 0;
+    hipError_t e = hipStreamGetCaptureInfo_v2((hipStream_t)stream, &status, nullptr, &graph, nullptr, nullptr);
+    if (e != hipSuccess || status != hipStreamCaptureStatusActive || !graph) return (int)e;
+    size_t n = 0;
+    e = hipGraphGetNodes(graph, nullptr, &n);
+    *nodes = (long)n;
+    return (int)e;
+}
+
 // ---- ABI self-description (include/c2m_geom.h): the ctypes host parses the header it ships with and refuses a library that was
 // built from another one (c2m_amd/_lib.py)
 C2M_API int c2m_abi_version(void) { return C2M_ABI_VERSION; }

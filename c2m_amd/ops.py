@@ -3700,3 +3700,139 @@ def map_quality(pred, gt, num_classes, thing_list, label_divisor, ignore_label, 
                                      _p(over), _p(work), nbytes, N, pl.H, pl.W, C, pl.label_divisor, pl.ignore_label,
                                      pl.max_pairs, _stream()), "map_quality")
     return {"tp": tp, "fp": fp, "fn": fn, "iou": iou, "confusion": conf, "overflow": over.view(torch.bool)}
+
+
+# =============================================================================================== connected components, instances
+# (csrc/components.hip; c2m_amd.segment.semantic_instances is the public interface of the second)
+COMPONENTS_TILE = (16, 64)          # c2m_components_tile_h/w(): the tile labelled in LDS; larger frames are merged across its seams
+SEMANTIC_INSTANCES_MAX_THINGS = 32
+_ComponentsPlan = collections.namedtuple("_ComponentsPlan", "N H W key_bytes stride_n stride_y connectivity")
+_InstancesPlan = collections.namedtuple("_InstancesPlan", "N H W things label_divisor ignore_label connectivity min_area")
+_THING_TABLES = {}
+
+
+def _components_plan(keys, connectivity):
+    """Every check of connected_components, made before anything is launched (host tensors pass: the device is the launch path's
+    check).  keys: uint8 or int32 [N,H,W] whose rows are dense (stride 1 along x); the other two strides are free."""
+    if not isinstance(keys, torch.Tensor):
+        raise ValueError(f"keys must be a tensor, got {type(keys).__name__}")
+    if keys.dtype not in (torch.uint8, torch.int32):
+        raise ValueError(f"keys must be uint8 or int32, got {keys.dtype}")
+    if keys.dim() != 3:
+        raise ValueError(f"keys must be [N,H,W], got {tuple(keys.shape)}")
+    N, H, W = keys.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31 or N * H * W >= 2 ** 31:
+        raise ValueError(f"{N} images of {H}x{W} pixels: an image is empty or too large (H * W and N * H * W must be below 2**31)")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    sn, sy, sx = keys.stride()
+    if (W > 1 and sx != 1) or (H > 1 and sy < 0) or (N > 1 and sn < 0):
+        raise ValueError(f"keys must have dense rows (stride 1 along x) and no negative stride, got strides {keys.stride()}")
+    return _ComponentsPlan(N, H, W, keys.element_size(), sn if N > 1 else 0, sy if H > 1 else W, int(connectivity))
+
+
+def _components_workspace(workspace, nbytes, dev, what):
+    """The int32 workspace of a call: a fresh block, or the caller's (tests hand in a poisoned one) if it is large enough."""
+    if workspace is None:
+        return torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    if not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.int32 and workspace.is_contiguous()
+            and workspace.device == dev and workspace.numel() * 4 >= nbytes):
+        raise ValueError(f"{what}: workspace must be a contiguous int32 tensor of at least {nbytes} bytes on {dev}")
+    return workspace
+
+
+def connected_components(keys, connectivity=8, workspace=None):
+    """Connected components of N key maps (csrc/components.hip; the contract is in include/c2m_hip.h and DESIGN.md 4.2o).
+    keys: uint8 or int32 [N,H,W] on the device, a view with dense rows is fine.  Two pixels belong to one component when they are
+    4- or 8-neighbours and carry the same key; there is no background.  Returns int32 [N,H,W]: at every pixel the index y * W + x
+    of its component's first pixel in raster order (scipy.ndimage.label up to renumbering).  Three launches on the current stream
+    whatever N is; nothing is read back and nothing synchronises; bit-repeatable; an image does not depend on the others."""
+    pl = _components_plan(keys, connectivity)
+    _hip_only(keys)
+    _on_current_device(keys)
+    L = _lib.lib()
+    assert (L.c2m_components_tile_h(), L.c2m_components_tile_w()) == COMPONENTS_TILE
+    keys = keys.detach()
+    out = torch.empty(pl.N, pl.H, pl.W, device=keys.device, dtype=torch.int32)
+    if pl.N:
+        nbytes = L.c2m_components_workspace_bytes(pl.N, pl.H, pl.W)
+        if nbytes < 0:
+            raise ValueError(f"connected_components: sizes out of range (N={pl.N}, {pl.H}x{pl.W})")
+        work = _components_workspace(workspace, nbytes, keys.device, "connected_components")
+        _lib.check(L.c2m_connected_components(_p(keys), pl.key_bytes, pl.stride_n, pl.stride_y, _p(out), _p(work), nbytes, pl.N,
+                                              pl.H, pl.W, pl.connectivity, _stream()), "connected_components")
+    return out
+
+
+def _instances_plan(labels, thing_list, label_divisor, ignore_label, connectivity, min_area):
+    """Every check of semantic_instances, made before anything is launched (host tensors pass: the device is the launch path's
+    check).  labels: uint8 or int64 [N,H,W] with values in 0..255."""
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError(f"labels must be a tensor, got {type(labels).__name__}")
+    if labels.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"labels must be uint8 or int64, got {labels.dtype}")
+    if labels.dim() != 3:
+        raise ValueError(f"labels must be [N,H,W], got {tuple(labels.shape)}")
+    N, H, W = labels.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31 or N * H * W >= 2 ** 31:
+        raise ValueError(f"{N} frames of {H}x{W} pixels: a frame is empty or too large (H * W and N * H * W must be below 2**31)")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    try:
+        label_divisor, ignore_label, min_area = (int(v) for v in (label_divisor, ignore_label, min_area))
+        things = tuple(int(c) for c in thing_list)
+    except (TypeError, ValueError):
+        raise ValueError("label_divisor, ignore_label and min_area must be integers and thing_list a list of class ids") from None
+    if len(things) > SEMANTIC_INSTANCES_MAX_THINGS:
+        raise ValueError(f"thing_list holds {len(things)} classes, at most {SEMANTIC_INSTANCES_MAX_THINGS} are supported")
+    if len(set(things)) != len(things):
+        raise ValueError(f"thing_list must hold distinct classes, got {list(things)}")
+    if not 0 <= ignore_label <= 255:
+        raise ValueError(f"ignore_label must be in 0..255, got {ignore_label}")
+    if any(not 0 <= c <= 255 for c in things) or ignore_label in things:
+        raise ValueError(f"thing_list must lie in 0..255 and leave out ignore_label={ignore_label}, got {list(things)}")
+    if label_divisor < 1 or 256 * label_divisor >= 2 ** 31:
+        raise ValueError(f"label_divisor={label_divisor} is out of range: class * label_divisor + n must stay below 2**31")
+    if min_area < 1:
+        raise ValueError(f"min_area must be at least 1, got {min_area}")
+    return _InstancesPlan(N, H, W, things, label_divisor, ignore_label, int(connectivity), min_area)
+
+
+def _thing_table(things, device):
+    """Device uint8 [256] of a thing list in the order given: 0 for no thing, else 1 + the position in the list."""
+    key = (things, device.index)
+    if key not in _THING_TABLES:
+        tab = np.zeros(256, np.uint8)
+        for i, c in enumerate(things):
+            tab[c] = i + 1
+        _THING_TABLES[key] = torch.from_numpy(tab).to(device)
+    return _THING_TABLES[key]
+
+
+def semantic_instances(labels, thing_list, label_divisor, ignore_label, connectivity=8, min_area=1, workspace=None):
+    """Instance ids of N label maps by connected components of the thing classes (csrc/components.hip; the contract is in
+    include/c2m_hip.h and DESIGN.md 4.2o).  labels: uint8 or int64 [N,H,W] with values in 0..255.  Returns device tensors:
+    instance int32 [N,H,W] (class * label_divisor + n on a kept thing component, n = 1, 2, ... per class and image by ascending
+    first raster pixel; the label everywhere else), count and dropped int32 [N, len(thing_list)], components int32 [N,H,W].  A
+    zero-fill and eight launches on the current stream; nothing is read back and nothing synchronises."""
+    pl = _instances_plan(labels, thing_list, label_divisor, ignore_label, connectivity, min_area)
+    _hip_only(labels)
+    _on_current_device(labels)
+    L = _lib.lib()
+    dev, N, H, W, T = labels.device, pl.N, pl.H, pl.W, len(pl.things)
+    labels = labels.detach()
+    labels = _f(labels if labels.dtype == torch.uint8 else labels.to(torch.uint8))
+    ins = torch.empty(N, H, W, device=dev, dtype=torch.int32)
+    comp = torch.empty(N, H, W, device=dev, dtype=torch.int32)
+    count = torch.empty(N, T, device=dev, dtype=torch.int32)
+    dropped = torch.empty(N, T, device=dev, dtype=torch.int32)
+    if N:
+        nbytes = L.c2m_semantic_instances_workspace_bytes(N, H, W, T)
+        if nbytes < 0:
+            raise ValueError(f"semantic_instances: sizes out of range (N={N}, {H}x{W}, {T} thing classes)")
+        work = _components_workspace(workspace, nbytes, dev, "semantic_instances")
+        table = _thing_table(pl.things, dev)
+        _lib.check(L.c2m_semantic_instances(_p(labels), _p(table), T, _p(ins), _p(comp), _p(count), _p(dropped), _p(work), nbytes,
+                                            N, H, W, pl.connectivity, pl.min_area, pl.label_divisor, _stream()),
+                   "semantic_instances")
+    return {"instance": ins, "count": count, "dropped": dropped, "components": comp}

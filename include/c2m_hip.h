@@ -631,6 +631,34 @@ int c2m_panoptic_maps(const float* logits, const uint8_t* labels, int C, const f
                       long workspace_bytes, int N, int H, int W, float threshold, int nms_kernel, int top_k, int label_divisor,
                       int stuff_area, int ignore_label, void* stream);
 
+/* ---- Connected components and instances from label maps (components.hip; ops.connected_components, c2m_amd.segment) ----------
+ * The reference has no counterpart: it reads instance ids a network produced.  keys: N images of H x W, uint8 (key_bytes 1) or
+ * int32 (key_bytes 4), rows dense (x stride 1), stride_y and stride_n in elements (>= 0; the keys are only read).  Two pixels
+ * belong to one component when they are `connectivity` (4 or 8) neighbours and carry the same key; there is no background.
+ * labels int32 [N][H][W]: at every pixel the index y * W + x of its component's first pixel in raster order -- a function of the
+ * input alone, and of its own image alone.  H, W >= 1, H * W < 2^31, N * H * W < 2^31.  workspace:
+ * c2m_components_workspace_bytes(N, H, W) bytes (-1 for sizes out of range), int32-aligned, nothing in it need be initialised.
+ * Three launches on `stream` whatever N is (64 x 16 tiles in LDS, a lock-free union by minimum index across the tile seams,
+ * a flatten pass); no kernel waits for another workgroup's write, no synchronisation, no copy to the host, bit-repeatable.
+ *
+ * c2m_semantic_instances: labels uint8 [N][H][W] dense; class_table device uint8 [256], 0 or 1 + the position of the class in
+ * the thing list (n_things <= 32).  components [N][H][W]: the operator's result on the labels.  A component of a thing class
+ * with at least min_area (>= 1) pixels qualifies; the qualifying components of a class in an image are numbered n = 1, 2, ... by
+ * ascending first raster pixel, and the first label_divisor - 1 of them are kept.  instance [N][H][W]: class * label_divisor + n
+ * on a kept component, else the label (stuff, ignore_label, small components, components past the cap).  count, dropped
+ * [N][n_things]: kept components, and qualifying ones past the cap.  label_divisor >= 1, 256 * label_divisor < 2^31.
+ * workspace: c2m_semantic_instances_workspace_bytes(N, H, W, n_things) bytes (-1 out of range); the call zeroes what it adds into.
+ * A zero-fill and eight launches on `stream`; int32 atomics only, so every output is exact and bit-repeatable.                 */
+int c2m_components_tile_w(void);
+int c2m_components_tile_h(void);
+long c2m_components_workspace_bytes(int N, int H, int W);
+int c2m_connected_components(const void* keys, int key_bytes, long stride_n, long stride_y, int32_t* labels, void* workspace,
+                             long workspace_bytes, int N, int H, int W, int connectivity, void* stream);
+long c2m_semantic_instances_workspace_bytes(int N, int H, int W, int n_things);
+int c2m_semantic_instances(const uint8_t* labels, const uint8_t* class_table, int n_things, int32_t* instance,
+                           int32_t* components, int32_t* count, int32_t* dropped, void* workspace, long workspace_bytes, int N,
+                           int H, int W, int connectivity, int min_area, int label_divisor, void* stream);
+
 /* ---- Scoring of label maps (map_quality.hip; c2m_amd.evaluate.map_quality) ------------------------------------------------------
  * Panoptic-quality counts and the confusion matrix of N predicted maps against N ground-truth maps, per image, as the reference's
  * pq_compute_single_core (cityscapesscripts/evaluation/evalPanopticSemanticLabeling.py) and SemanticEvaluator.update compute them
@@ -704,6 +732,9 @@ int c2m_event_create(void** event_out);
 int c2m_event_record(void* event, void* stream);
 int c2m_event_elapsed_ms(void* start, void* stop, float* ms);
 int c2m_event_destroy(void* event);
+/* For the tests of "a fixed number of launches": the number of nodes the graph capture on `stream` has recorded so far (0 when
+ * the stream is not capturing); the difference around a call is what the call put on the stream.                     */
+int c2m_capture_node_count(void* stream, long* nodes);
 
 /* ---- optimizer (optim.hip): SURVEY §8f-1 --------------------------------------------------------------------
  * The four torch.optim.Adam(betas=(0.5,0.999), eps=1e-7) of modules/model.py:54-99, stepped at trainer/trainer.py:155-165:
