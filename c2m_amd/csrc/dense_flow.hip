@@ -17,6 +17,11 @@
 //                           1 / max(1, |residual of that patch at this pixel|).  No atomics.  With shift > 0 it writes the flow of a
 //                           coarser level straight at the size of level 0 (2^shift * f[y >> shift][x >> shift]).
 //
+// Segment guide: the <true> instantiations of the search and the densify read the level-0 id map of frame a
+// (level l reads it at (y << l, x << l)).  A patch sum runs over the lanes whose id is that of the patch centre, a pixel is
+// averaged over the covering patches whose centre has its id; a record gains the lane count n as a fourth float.  The <false>
+// instantiations are the code above, untouched.
+//
 // The window of b that a patch samples is read through L1 / L2, not staged in LDS: a level image of the training
 // size is <= 128 KB, a patch touches about 9 x 9 floats of it per step, and with no early exit the flow is bounded only at the
 // END of the search (step 6), so a staged 25 x 25 window would still need the global path next to it.
@@ -168,7 +173,25 @@ struct FlPsP {
     long waves;                                                                 // N * npy * npx: one wave each
 };
 
-__global__ __launch_bounds__(256) void fl_patch_search_kernel(const FlPsP p) {
+// the guide: ids [N][H][W] of level 0; the id of level pixel (y, x) is ids[y << level][x << level], inside the map: checked by
+// the launchers
+struct FlSegP {
+    const int32_t* ids;
+    int level, W;
+    long plane;                                                                 // H * W
+    __device__ __forceinline__ int at(long n, int y, int x) const {
+        return ids[n * plane + (long)(y << level) * W + (x << level)];
+    }
+};
+
+static inline bool fl_seg_ok(const int32_t* ids, long elems, long N, int level, int H, int W, int h, int w) {
+    return level >= 0 && level < C2M_FLOW_MAX_LEVELS && H >= 1 && W >= 1 && H <= C2M_FLOW_MAX_SIDE && W <= C2M_FLOW_MAX_SIDE &&
+           ((long)(h - 1) << level) < H && ((long)(w - 1) << level) < W && (N == 0 || (ids && elems >= N * (long)H * W &&
+           c2m_aligned(4, ids)));
+}
+
+template <bool G>
+__global__ __launch_bounds__(256) void fl_patch_search_kernel(const FlPsP p, const FlSegP g) {
     const int lane = threadIdx.x & 63, py = lane >> 3, px = lane & 7;
     const int h = p.h, w = p.w;
     const long nwaves = (long)gridDim.x * 4;
@@ -193,16 +216,28 @@ __global__ __launch_bounds__(256) void fl_patch_search_kernel(const FlPsP p) {
             u0 = s * F[0];
             v0 = s * F[(long)p.hc * p.wc];
         }
-        const float mT = wave_sum_all(T) * 0.015625f, Tm = T - mT;
-        const float a = wave_sum_all(gx * gx), b = wave_sum_all(gx * gy), c = wave_sum_all(gy * gy);
+        // guided: the lanes whose id is that of the patch centre (the pixel the initial flow is read at) carry the sums, the
+        // others add 0.f in the same shuffle order; cnt >= 1, the centre lane
+        bool in = true;
+        float cnt = 64.f, det_min = C2M_FLOW_DET_MIN;
+        if constexpr (G) {
+            in = g.at(n, y, x) == g.at(n, oy + 3, ox + 3);
+            const int k = wave_count(in);
+            cnt = (float)k;
+            det_min = C2M_FLOW_DET_MIN * ((float)(k * k) / 4096.f);
+        }
+        auto part = [&](float v) { if constexpr (G) return in ? v : 0.f; else return v; };
+        auto mean = [&](float s) { if constexpr (G) return s / cnt; else return s * 0.015625f; };
+        const float mT = mean(wave_sum_all(part(T))), Tm = T - mT;
+        const float a = wave_sum_all(part(gx * gx)), b = wave_sum_all(part(gx * gy)), c = wave_sum_all(part(gy * gy));
         const float det = a * c - b * b;
         float u = u0, v = v0;
-        if (det > C2M_FLOW_DET_MIN) {                                           // wave-uniform: every lane holds lane 0's sums
+        if (det > det_min) {                                                    // wave-uniform: every lane holds lane 0's sums
             for (int it = 0; it < p.iters; ++it) {
                 const float J = fl_sample(B, h, w, (float)x + u, (float)y + v);
-                const float mJ = wave_sum_all(J) * 0.015625f;
+                const float mJ = mean(wave_sum_all(part(J)));
                 const float r = (J - mJ) - Tm;
-                const float bx = wave_sum_all(r * gx), by = wave_sum_all(r * gy);
+                const float bx = wave_sum_all(part(r * gx)), by = wave_sum_all(part(r * gy));
                 u -= (c * bx - b * by) / det;
                 v -= (a * by - b * bx) / det;
             }
@@ -210,17 +245,19 @@ __global__ __launch_bounds__(256) void fl_patch_search_kernel(const FlPsP p) {
             if (!(du * du + dv * dv <= C2M_FLOW_MAX_STEP2)) { u = u0; v = v0; } // further than 8 px (or NaN): back to the initial flow
         }
         const float J = fl_sample(B, h, w, (float)x + u, (float)y + v);
-        const float mJ = wave_sum_all(J) * 0.015625f;
+        const float mJ = mean(wave_sum_all(part(J)));
         if (lane == 0) {
-            float* __restrict__ o = p.rec + i * 3;
+            float* __restrict__ o = p.rec + i * (G ? 4 : 3);
             o[0] = u; o[1] = v; o[2] = mJ - mT;
+            if constexpr (G) o[3] = cnt;
         }
     }
 }
 
-C2M_API int c2m_flow_patch_search(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
-                                  int init_shift, float* records, long record_elems, int N, int h, int w, int iters, void* stream) {
-    C2M_ENTER();
+// ids NULL: the unguided search (records of 3 floats); else the guided one (4 floats)
+static int fl_patch_search(const float* ia, const float* ib, long image_elems, const float* init, long init_elems, int init_shift,
+                           float* records, long record_elems, int N, int h, int w, int iters, const int32_t* ids, int level,
+                           int H, int W, void* stream) {
     if (!fl_level_ok(N, h, w) || iters < 0 || iters > C2M_FLOW_MAX_ITERS || init_shift < 0 || init_shift > 1)
         return (int)hipErrorInvalidValue;
     if (N == 0) return 0;
@@ -230,11 +267,30 @@ C2M_API int c2m_flow_patch_search(const float* ia, const float* ib, long image_e
     p.hc = (h + (1 << init_shift) - 1) >> init_shift; p.wc = (w + (1 << init_shift) - 1) >> init_shift;
     p.shift = init_shift; p.iters = iters;
     p.waves = (long)N * p.npy * p.npx;
-    if (!ia || !ib || !records || image_elems < (long)N * h * w || record_elems < p.waves * 3 ||
+    if (!ia || !ib || !records || image_elems < (long)N * h * w || record_elems < p.waves * (ids ? 4 : 3) ||
         (init && init_elems < 2L * N * p.hc * p.wc) || !c2m_aligned(4, ia, ib, init, records))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(fl_patch_search_kernel, dim3(c2m_grid(p.waves * 64, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    const FlSegP g = {ids, level, W, (long)H * W};
+    const dim3 grid(c2m_grid(p.waves * 64, 256));
+    if (ids) hipLaunchKernelGGL(fl_patch_search_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
+    else hipLaunchKernelGGL(fl_patch_search_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
     return (int)hipGetLastError();
+}
+
+C2M_API int c2m_flow_patch_search(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
+                                  int init_shift, float* records, long record_elems, int N, int h, int w, int iters, void* stream) {
+    C2M_ENTER();
+    return fl_patch_search(ia, ib, image_elems, init, init_elems, init_shift, records, record_elems, N, h, w, iters, nullptr, 0, 0,
+                           0, stream);
+}
+
+C2M_API int c2m_flow_patch_search_guided(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
+                                         int init_shift, float* records, long record_elems, int N, int h, int w, int iters,
+                                         const int32_t* segments, long segment_elems, int level, int H, int W, void* stream) {
+    C2M_ENTER();
+    if (!fl_level_ok(N, h, w) || !fl_seg_ok(segments, segment_elems, N, level, H, W, h, w)) return (int)hipErrorInvalidValue;
+    return fl_patch_search(ia, ib, image_elems, init, init_elems, init_shift, records, record_elems, N, h, w, iters, segments,
+                           level, H, W, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ densify
@@ -245,7 +301,8 @@ struct FlDnP {
     long total;                                                                 // N * Ho * Wo
 };
 
-__global__ __launch_bounds__(256) void fl_densify_kernel(const FlDnP p) {
+template <bool G>
+__global__ __launch_bounds__(256) void fl_densify_kernel(const FlDnP p, const FlSegP g) {
     const int h = p.h, w = p.w;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < p.total; i += (long)gridDim.x * blockDim.x) {
         const int X = (int)(i % p.Wo);
@@ -255,25 +312,39 @@ __global__ __launch_bounds__(256) void fl_densify_kernel(const FlDnP p) {
         const int x = X >> p.shift, y = Y >> p.shift;                           // < w, h: checked by the launcher
         const float* __restrict__ A = p.ia + n * ((long)h * w);
         const float* __restrict__ B = p.ib + n * ((long)h * w);
-        const float* __restrict__ R = p.rec + n * 3 * ((long)p.npy * p.npx);
+        constexpr int RW = G ? 4 : 3;
+        const float* __restrict__ R = p.rec + n * RW * ((long)p.npy * p.npx);
         const float T = A[(long)y * w + x];
+        int id = 0;
+        if constexpr (G) id = g.at(n, y, x);
         // a patch of index j has its origin at min(4 j, n - 8): the indices whose 8 pixels can hold y are ceil((y - 7) / 4) ..
         // y / 4 + 1 (the last, clamped, patch); the test against the origin picks the <= 3 that do
         const int jy0 = y < 4 ? 0 : (y - 4) >> 2, jy1 = min((y >> 2) + 1, p.npy - 1);
         const int jx0 = x < 4 ? 0 : (x - 4) >> 2, jx1 = min((x >> 2) + 1, p.npx - 1);
         float su = 0.f, sv = 0.f, sw = 0.f;
+        float au = 0.f, av = 0.f, aw = 0.f;                                     // guided: over ALL covering patches, the fall-back
+        bool own = false;                                                       // guided: a covering patch has this pixel's id
         for (int jy = jy0; jy <= jy1; ++jy) {                                   // ascending (oy, ox): the order of the sum is fixed
             const int oy = min(C2M_FLOW_STRIDE * jy, h - C2M_FLOW_PATCH);
             if (y < oy || y > oy + C2M_FLOW_PATCH - 1) continue;
             for (int jx = jx0; jx <= jx1; ++jx) {
                 const int ox = min(C2M_FLOW_STRIDE * jx, w - C2M_FLOW_PATCH);
                 if (x < ox || x > ox + C2M_FLOW_PATCH - 1) continue;
-                const float* __restrict__ q = R + 3 * ((long)jy * p.npx + jx);
+                const float* __restrict__ q = R + RW * ((long)jy * p.npx + jx);
                 const float u = q[0], v = q[1], d = q[2];
                 const float r = (fl_sample(B, h, w, (float)x + u, (float)y + v) - T) - d;
-                const float wgt = 1.f / fmaxf(1.f, fabsf(r));
-                su += wgt * u; sv += wgt * v; sw += wgt;
+                if constexpr (G) {
+                    const float wgt = q[3] / fmaxf(1.f, fabsf(r));
+                    au += wgt * u; av += wgt * v; aw += wgt;
+                    if (g.at(n, oy + 3, ox + 3) == id) { su += wgt * u; sv += wgt * v; sw += wgt; own = true; }
+                } else {
+                    const float wgt = 1.f / fmaxf(1.f, fabsf(r));
+                    su += wgt * u; sv += wgt * v; sw += wgt;
+                }
             }
+        }
+        if constexpr (G) {
+            if (!own) { su = au; sv = av; sw = aw; }                            // e.g. a structure thinner than a stride
         }
         float* __restrict__ o = p.out + n * 2 * ((long)p.Ho * p.Wo) + (long)Y * p.Wo + X;
         o[0] = p.scale * (su / sw);                                             // sw > 0: every pixel is covered (h, w >= 8)
@@ -281,9 +352,9 @@ __global__ __launch_bounds__(256) void fl_densify_kernel(const FlDnP p) {
     }
 }
 
-C2M_API int c2m_flow_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
-                             float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, void* stream) {
-    C2M_ENTER();
+static int fl_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems, float* flow,
+                      long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, const int32_t* ids, int level, int H, int W,
+                      void* stream) {
     if (!fl_level_ok(N, h, w) || shift < 0 || shift >= C2M_FLOW_MAX_LEVELS || Ho < 1 || Wo < 1 || Ho > C2M_FLOW_MAX_SIDE ||
         Wo > C2M_FLOW_MAX_SIDE || ((Ho - 1) >> shift) >= h || ((Wo - 1) >> shift) >= w)
         return (int)hipErrorInvalidValue;
@@ -293,9 +364,27 @@ C2M_API int c2m_flow_densify(const float* ia, const float* ib, long image_elems,
     p.h = h; p.w = w; p.npy = fl_patches(h); p.npx = fl_patches(w); p.shift = shift; p.Ho = Ho; p.Wo = Wo;
     p.scale = (float)(1 << shift);
     p.total = (long)N * Ho * Wo;
-    if (!ia || !ib || !records || !flow || image_elems < (long)N * h * w || record_elems < 3L * N * p.npy * p.npx ||
-        flow_elems < 2 * p.total || !c2m_aligned(4, ia, ib, records, flow))
+    if (!ia || !ib || !records || !flow || image_elems < (long)N * h * w ||
+        record_elems < (ids ? 4L : 3L) * N * p.npy * p.npx || flow_elems < 2 * p.total || !c2m_aligned(4, ia, ib, records, flow))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(fl_densify_kernel, dim3(c2m_grid(p.total, 256)), dim3(256), 0, (hipStream_t)stream, p);
+    const FlSegP g = {ids, level, W, (long)H * W};
+    const dim3 grid(c2m_grid(p.total, 256));
+    if (ids) hipLaunchKernelGGL(fl_densify_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
+    else hipLaunchKernelGGL(fl_densify_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
     return (int)hipGetLastError();
+}
+
+C2M_API int c2m_flow_densify(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
+                             float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo, void* stream) {
+    C2M_ENTER();
+    return fl_densify(ia, ib, image_elems, records, record_elems, flow, flow_elems, N, h, w, shift, Ho, Wo, nullptr, 0, 0, 0, stream);
+}
+
+C2M_API int c2m_flow_densify_guided(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
+                                    float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo,
+                                    const int32_t* segments, long segment_elems, int level, int H, int W, void* stream) {
+    C2M_ENTER();
+    if (!fl_level_ok(N, h, w) || !fl_seg_ok(segments, segment_elems, N, level, H, W, h, w)) return (int)hipErrorInvalidValue;
+    return fl_densify(ia, ib, image_elems, records, record_elems, flow, flow_elems, N, h, w, shift, Ho, Wo, segments, level, H, W,
+                      stream);
 }

@@ -19,6 +19,7 @@
 // LDS of fr_iterate_kernel, sor <= 5 (halo 10): 11 planes (du, dv, u, v, b1, b2, A12, A11 + sw, A22 + sw, wR, wD) of 52 x 52
 // floats = 118 976 B, plus the smoothness weight ws on 54 x 54 = 11 664 B: 130 640 B of the CU's 163 840, one workgroup of 16
 // waves per CU.  The coefficients are computed on 52^2 / 32^2 = 2.64 x the pixels of the tile, the sweeps on 1.67 x.
+// The guided instantiation adds the ids of the 54 x 54 cells as an int plane, 11 664 B: 142 304 B.
 #include "common.h"
 #include "flow_sample.h"
 
@@ -124,10 +125,21 @@ struct FrItP {
 
 enum { FR_DU, FR_DV, FR_U, FR_V, FR_B1, FR_B2, FR_A12, FR_D1, FR_D2, FR_WR, FR_WD, FR_PLANES };
 
-__global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p) {
+// the guide: ids [N][H][W] of level 0; the id of level pixel (y, x) is ids[y << level][x << level], inside the
+// map: checked by the launcher.  No smoothness couples two ids: a forward difference toward another id counts as 0 in ws, and
+// the weight of an edge between two ids is 0.
+struct FrSegP {
+    const int32_t* ids;
+    int level, W;
+    long plane;                                                                 // H * W
+};
+
+template <bool G>
+__global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p, const FrSegP g) {
     constexpr int T = C2M_FR_TILE, RS = C2M_FR_RS, WS = C2M_FR_WS;
     __shared__ float s_ws[WS * WS];
     __shared__ float s[FR_PLANES][RS * RS];
+    __shared__ int s_id[G ? WS * WS : 1];                                       // guided: the ids of the cells of s_ws
     const int tid = threadIdx.x, h = p.h, w = p.w, tiles = p.ty * p.tx;
     const int tile = (int)(blockIdx.x % (unsigned)tiles), n = (int)(blockIdx.x / (unsigned)tiles);
     const int ty0 = (tile / p.tx) * T, tx0 = (tile % p.tx) * T;
@@ -146,8 +158,16 @@ __global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p) {
         if (gy < 0 || gy >= h || gx < 0 || gx >= w) continue;
         const long q = (long)gy * w + gx, qr = (long)gy * w + min(gx + 1, w - 1), qd = (long)min(gy + 1, h - 1) * w + gx;
         const float U = gu[q] + (gdu ? gdu[q] : 0.f), V = gv[q] + (gdv ? gdv[q] : 0.f);
-        const float Ux = (gu[qr] + (gdu ? gdu[qr] : 0.f)) - U, Uy = (gu[qd] + (gdu ? gdu[qd] : 0.f)) - U;
-        const float Vx = (gv[qr] + (gdv ? gdv[qr] : 0.f)) - V, Vy = (gv[qd] + (gdv ? gdv[qd] : 0.f)) - V;
+        float Ux = (gu[qr] + (gdu ? gdu[qr] : 0.f)) - U, Uy = (gu[qd] + (gdu ? gdu[qd] : 0.f)) - U;
+        float Vx = (gv[qr] + (gdv ? gdv[qr] : 0.f)) - V, Vy = (gv[qd] + (gdv ? gdv[qd] : 0.f)) - V;
+        if constexpr (G) {                                                      // the clamped neighbour of the last column / row is q itself
+            const int32_t* __restrict__ S = g.ids + n * g.plane;
+            const long row = (long)(gy << g.level) * g.W, rowd = (long)(min(gy + 1, h - 1) << g.level) * g.W;
+            const int id = S[row + (gx << g.level)];
+            if (S[row + (min(gx + 1, w - 1) << g.level)] != id) Ux = Vx = 0.f;
+            if (S[rowd + (gx << g.level)] != id) Uy = Vy = 0.f;
+            s_id[ly * WS + lx] = id;
+        }
         s_ws[ly * WS + lx] = p.alpha / sqrtf((((Ux * Ux + Uy * Uy) + Vx * Vx) + Vy * Vy) + C2M_FR_EPS2);
     }
     __syncthreads();
@@ -158,8 +178,14 @@ __global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p) {
         const long q = (long)gy * w + gx;
         const int c = ly * RS + lx, cw = (ly + 1) * WS + (lx + 1);
         const float ws = s_ws[cw];
-        const float wR = gx < w - 1 ? 0.5f * (ws + s_ws[cw + 1]) : 0.f, wD = gy < h - 1 ? 0.5f * (ws + s_ws[cw + WS]) : 0.f;
-        const float wL = gx > 0 ? 0.5f * (s_ws[cw - 1] + ws) : 0.f, wU = gy > 0 ? 0.5f * (s_ws[cw - WS] + ws) : 0.f;
+        bool eR = gx < w - 1, eD = gy < h - 1, eL = gx > 0, eU = gy > 0;        // the edges of the smoothness graph at this pixel
+        if constexpr (G) {                                                      // the cell of a neighbour inside the image holds its id
+            const int id = s_id[cw];
+            eR = eR && s_id[cw + 1] == id; eD = eD && s_id[cw + WS] == id;
+            eL = eL && s_id[cw - 1] == id; eU = eU && s_id[cw - WS] == id;
+        }
+        const float wR = eR ? 0.5f * (ws + s_ws[cw + 1]) : 0.f, wD = eD ? 0.5f * (ws + s_ws[cw + WS]) : 0.f;
+        const float wL = eL ? 0.5f * (s_ws[cw - 1] + ws) : 0.f, wU = eU ? 0.5f * (s_ws[cw - WS] + ws) : 0.f;
         const float sw = ((wL + wR) + wU) + wD;
         const float du = gdu ? gdu[q] : 0.f, dv = gdv ? gdv[q] : 0.f;
         const float Ix = pl[q], Iy = pl[P + q], Iz = pl[2 * P + q], Ixx = pl[3 * P + q], Ixy = pl[4 * P + q], Iyy = pl[5 * P + q],
@@ -199,8 +225,14 @@ __global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p) {
             const float sv = (((wL * (s[FR_V][cl] + s[FR_DV][cl]) + wR * (s[FR_V][cr] + s[FR_DV][cr])) +
                                wU * (s[FR_V][cu] + s[FR_DV][cu])) + wD * (s[FR_V][cd] + s[FR_DV][cd])) - sw * s[FR_V][c];
             const float A12 = s[FR_A12][c];
-            const float du = om1 * s[FR_DU][c] + p.omega * (((s[FR_B1][c] + su) - A12 * s[FR_DV][c]) / s[FR_D1][c]);
-            const float dv = om1 * s[FR_DV][c] + p.omega * (((s[FR_B2][c] + sv) - A12 * du) / s[FR_D2][c]);
+            float du = om1 * s[FR_DU][c] + p.omega * (((s[FR_B1][c] + su) - A12 * s[FR_DV][c]) / s[FR_D1][c]);
+            if constexpr (G) {                                                  // all edges cut and a flat image: D1 = A11 = 0, du stays
+                if (!(s[FR_D1][c] > 0.f)) du = s[FR_DU][c];
+            }
+            float dv = om1 * s[FR_DV][c] + p.omega * (((s[FR_B2][c] + sv) - A12 * du) / s[FR_D2][c]);
+            if constexpr (G) {
+                if (!(s[FR_D2][c] > 0.f)) dv = s[FR_DV][c];
+            }
             s[FR_DU][c] = du; s[FR_DV][c] = dv;
         }
     }
@@ -228,10 +260,10 @@ __global__ __launch_bounds__(1024) void fr_iterate_kernel(const FrItP p) {
     }
 }
 
-C2M_API int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h, int w,
-                                    int iteration, int sor, float alpha, float delta, float gamma, float omega, float* out,
-                                    long out_elems, int shift, int Ho, int Wo, void* stream) {
-    C2M_ENTER();
+// ids NULL: the unguided iteration
+static int fr_iterate(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h, int w, int iteration,
+                      int sor, float alpha, float delta, float gamma, float omega, float* out, long out_elems, int shift, int Ho,
+                      int Wo, const int32_t* ids, int level, int H, int W, void* stream) {
     auto weight = [](float v) { return v > 0.f && v < 3.0e38f; };               // false for a NaN
     if (!fr_level_ok(N, h, w) || iteration < 0 || iteration >= C2M_FR_MAX_OUTER || sor < 1 || sor > C2M_FR_MAX_SOR ||
         !weight(alpha) || !weight(delta) || !weight(gamma) || !(omega > 0.f && omega < 2.f))
@@ -253,6 +285,29 @@ C2M_API int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* wo
     if (!flow || !workspace || flow_elems < 2 * P || workspace_bytes < 12 * P * 4 || blocks >= (1L << 31) ||
         (out && out_elems < 2L * N * Ho * Wo) || !c2m_aligned(4, flow, workspace, out))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(fr_iterate_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, p);
+    const FrSegP g = {ids, level, W, (long)H * W};
+    if (ids) hipLaunchKernelGGL(fr_iterate_kernel<true>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, p, g);
+    else hipLaunchKernelGGL(fr_iterate_kernel<false>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, p, g);
     return (int)hipGetLastError();
+}
+
+C2M_API int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h, int w,
+                                    int iteration, int sor, float alpha, float delta, float gamma, float omega, float* out,
+                                    long out_elems, int shift, int Ho, int Wo, void* stream) {
+    C2M_ENTER();
+    return fr_iterate(flow, flow_elems, workspace, workspace_bytes, N, h, w, iteration, sor, alpha, delta, gamma, omega, out,
+                      out_elems, shift, Ho, Wo, nullptr, 0, 0, 0, stream);
+}
+
+C2M_API int c2m_flow_refine_iterate_guided(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h,
+                                           int w, int iteration, int sor, float alpha, float delta, float gamma, float omega,
+                                           float* out, long out_elems, int shift, int Ho, int Wo, const int32_t* segments,
+                                           long segment_elems, int level, int H, int W, void* stream) {
+    C2M_ENTER();
+    if (!fr_level_ok(N, h, w) || level < 0 || level > C2M_FR_MAX_SHIFT || H < 1 || W < 1 || H > C2M_FR_MAX_SIDE ||
+        W > C2M_FR_MAX_SIDE || ((long)(h - 1) << level) >= H || ((long)(w - 1) << level) >= W ||
+        (N > 0 && (!segments || segment_elems < (long)N * H * W || !c2m_aligned(4, segments))))
+        return (int)hipErrorInvalidValue;
+    return fr_iterate(flow, flow_elems, workspace, workspace_bytes, N, h, w, iteration, sor, alpha, delta, gamma, omega, out,
+                      out_elems, shift, Ho, Wo, segments, level, H, W, stream);
 }

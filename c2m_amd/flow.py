@@ -11,7 +11,9 @@ per patch and a weighted average of the patches that cover a pixel.  `refine=Tru
 flow (csrc/flow_refine.hip; off by default).  A motion of more than about 8 px at the coarsest level (25 px at
 128 x 256, four levels) is out of range of ONE search; frames of a clip that are further apart get their flow from the flows
 between consecutive frames, chained (`chain_flows`, `clip_flows`, `ClassicFlow(chain=True)`; csrc/flow_chain.hip; DESIGN.md
-4.2n).  Nothing here has weights; nothing is differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
+4.2n).  `segments=` (the int32 instance ids of frame a) keeps the motion of one id out of the estimate of another: patch sums,
+the average over patches and the refinement's smoothness stop at id borders (DESIGN.md 4.2p).  Nothing here has weights;
+nothing is differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
 """
 import torch
 import torch.nn as nn
@@ -73,6 +75,23 @@ def _level_images(ia, ib):
     return ia.detach().contiguous(), ib.detach().contiguous()
 
 
+def _segment_ids(segments, N, h, w, level, device):
+    """The checks of a guide: int32 [N,H,W] on `device`, the ids of frame a at level 0, which a stage on level `level` with
+    [N,h,w] images reads at (y << level, x << level).  None stays None."""
+    if segments is None:
+        return None
+    level = int(level)
+    if not isinstance(segments, torch.Tensor) or segments.dtype != torch.int32 or segments.dim() != 3 or segments.shape[0] != N:
+        raise ValueError(f"segments must be an int32 [{N},H,W] tensor, got {getattr(segments, 'dtype', None)} "
+                         f"{list(getattr(segments, 'shape', ()))}")
+    if segments.device != device:
+        raise ValueError(f"segments must be on the device of the images ({device}), got {segments.device}")
+    H, W = segments.shape[1:]
+    if not 0 <= level < MAX_LEVELS or ((h - 1) << level) >= H or ((w - 1) << level) >= W:
+        raise ValueError(f"segments {[H, W]} is not the level-0 map of a level-{level} image of {[h, w]}")
+    return segments.detach().contiguous()
+
+
 def flow_pyramid(a, b, value_range=(0, 1), levels=None):
     """Gray pyramids of both frames of N pairs in one launch -> (workspace, sizes, images): `workspace` is the fp32 buffer of
     one dense_flow call (c2m_flow_workspace_bytes), sizes = pyramid_sizes, images[l] = (a_l, b_l), [N,h,w] views of it."""
@@ -96,12 +115,14 @@ def flow_pyramid(a, b, value_range=(0, 1), levels=None):
     return work, sizes, images
 
 
-def patch_search(ia, ib, init=None, iters=12, out=None):
+def patch_search(ia, ib, init=None, iters=12, out=None, segments=None, level=0):
     """Steps 1-6 for one level: ia, ib [N,h,w] fp32 -> records [N,npy,npx,3] = (u, v, mean(J) - mean(T)) per patch.  init: None
     (zero flow), the dense flow [N,2,h,w] of this level, or that of the coarser level [N,2,(h+1)//2,(w+1)//2], which is read as
-    2 * init[y // 2, x // 2]."""
+    2 * init[y // 2, x // 2].  segments: int32 [N,H,W], the ids of frame a at level 0 (ia is level `level` of it): every patch
+    sum runs over the pixels with the id of the patch centre, and the records are [N,npy,npx,4], the count n last."""
     ia, ib = _level_images(ia, ib)
     N, h, w = ia.shape
+    segments = _segment_ids(segments, N, h, w, level, ia.device)
     shift = 0
     if init is not None:
         coarse = (N, 2, (h + 1) // 2, (w + 1) // 2)
@@ -111,25 +132,39 @@ def patch_search(ia, ib, init=None, iters=12, out=None):
         shift = int(tuple(init.shape) != (N, 2, h, w))
         init = init.detach().contiguous()
     npy, npx = len(patch_origins(h)), len(patch_origins(w))
-    rec = torch.empty(N, npy, npx, 3, device=ia.device, dtype=torch.float32) if out is None else out
+    rec = torch.empty(N, npy, npx, 3 if segments is None else 4, device=ia.device, dtype=torch.float32) if out is None else out
+    if segments is not None:
+        _lib.check(_lib.lib().c2m_flow_patch_search_guided(
+            ops._p(ia), ops._p(ib), ia.numel(), ops._p(init), 0 if init is None else init.numel(), shift, ops._p(rec), rec.numel(),
+            N, h, w, int(iters), ops._p(segments), segments.numel(), int(level), segments.shape[1], segments.shape[2],
+            ops._stream()), "flow_patch_search_guided")
+        return rec
     _lib.check(_lib.lib().c2m_flow_patch_search(ops._p(ia), ops._p(ib), ia.numel(), ops._p(init), 0 if init is None else init.numel(),
                                                 shift, ops._p(rec), rec.numel(), N, h, w, int(iters), ops._stream()),
                "flow_patch_search")
     return rec
 
 
-def densify(ia, ib, records, shift=0, out_size=None, out=None):
+def densify(ia, ib, records, shift=0, out_size=None, out=None, segments=None, level=0):
     """Step 7 for one level: the dense flow [N,2,h,w] from the patch records [N,npy,npx,3].  shift, out_size: write
-    2**shift * flow[y >> shift, x >> shift] at out_size = (Ho, Wo) instead (a coarser level brought to level 0)."""
+    2**shift * flow[y >> shift, x >> shift] at out_size = (Ho, Wo) instead (a coarser level brought to level 0).  segments (as
+    in patch_search, with its records [N,npy,npx,4]): a pixel is averaged over the patches whose centre has its id."""
     ia, ib = _level_images(ia, ib)
     N, h, w = ia.shape
-    npy, npx = len(patch_origins(h)), len(patch_origins(w))
-    if not isinstance(records, torch.Tensor) or records.dtype != torch.float32 or tuple(records.shape) != (N, npy, npx, 3):
-        raise ValueError(f"records must be fp32 {[N, npy, npx, 3]}, got {list(getattr(records, 'shape', ()))}")
+    segments = _segment_ids(segments, N, h, w, level, ia.device)
+    npy, npx, width = len(patch_origins(h)), len(patch_origins(w)), 3 if segments is None else 4
+    if not isinstance(records, torch.Tensor) or records.dtype != torch.float32 or tuple(records.shape) != (N, npy, npx, width):
+        raise ValueError(f"records must be fp32 {[N, npy, npx, width]}, got {list(getattr(records, 'shape', ()))}")
     ops._hip_only(records)
     records = records.detach().contiguous()
     Ho, Wo = (h, w) if out_size is None else (int(v) for v in out_size)
     flow = torch.empty(N, 2, Ho, Wo, device=ia.device, dtype=torch.float32) if out is None else out
+    if segments is not None:
+        _lib.check(_lib.lib().c2m_flow_densify_guided(
+            ops._p(ia), ops._p(ib), ia.numel(), ops._p(records), records.numel(), ops._p(flow), flow.numel(), N, h, w, int(shift),
+            Ho, Wo, ops._p(segments), segments.numel(), int(level), segments.shape[1], segments.shape[2], ops._stream()),
+            "flow_densify_guided")
+        return flow
     _lib.check(_lib.lib().c2m_flow_densify(ops._p(ia), ops._p(ib), ia.numel(), ops._p(records), records.numel(), ops._p(flow),
                                            flow.numel(), N, h, w, int(shift), Ho, Wo, ops._stream()), "flow_densify")
     return flow
@@ -189,13 +224,21 @@ def refine_planes(ia, ib, flow, work=None):
     return work[:8 * N * h * w].view(8, N, h, w)
 
 
-def _refine_level(ia, ib, flow, p, work, out, shift=0):
-    """prepare + p['outer'] iterate launches; flow [N,2,h,w] contiguous; the last iteration writes `out` [N,2,Ho,Wo]."""
+def _refine_level(ia, ib, flow, p, work, out, shift=0, segments=None, level=0):
+    """prepare + p['outer'] iterate launches; flow [N,2,h,w] contiguous; the last iteration writes `out` [N,2,Ho,Wo].  segments
+    (checked by the caller): the smoothness is cut at the id borders of level `level`."""
     N, h, w = ia.shape
     refine_planes(ia, ib, flow, work)
     L, nbytes = _lib.lib(), work.numel() * 4
     for k in range(p["outer"]):
         last = k == p["outer"] - 1
+        if segments is not None:
+            _lib.check(L.c2m_flow_refine_iterate_guided(
+                ops._p(flow), flow.numel(), ops._p(work), nbytes, N, h, w, k, p["sor"], p["alpha"], p["delta"], p["gamma"],
+                p["omega"], ops._p(out) if last else None, out.numel() if last else 0, int(shift), out.shape[2], out.shape[3],
+                ops._p(segments), segments.numel(), int(level), segments.shape[1], segments.shape[2], ops._stream()),
+                "flow_refine_iterate_guided")
+            continue
         _lib.check(L.c2m_flow_refine_iterate(ops._p(flow), flow.numel(), ops._p(work), nbytes, N, h, w, k, p["sor"], p["alpha"],
                                              p["delta"], p["gamma"], p["omega"], ops._p(out) if last else None,
                                              out.numel() if last else 0, int(shift), out.shape[2], out.shape[3], ops._stream()),
@@ -203,22 +246,24 @@ def _refine_level(ia, ib, flow, p, work, out, shift=0):
     return out
 
 
-def refine_flow(ia, ib, flow, alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6, out=None):
+def refine_flow(ia, ib, flow, alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6, out=None, segments=None, level=0):
     """Variational refinement of one level: ia, ib [N,h,w] fp32 gray on 0..255 and the level's dense flow
     [N,2,h,w] -> the refined flow [N,2,h,w].  `outer` fixed-point iterations of `sor` (<= SOR_CAP) red-black SOR sweeps with
     relaxation omega; alpha, delta, gamma weigh smoothness, brightness and gradient constancy.  1 + outer launches on the
-    current stream, no synchronisation; bit-repeatable and independent of N."""
+    current stream, no synchronisation; bit-repeatable and independent of N.  segments: int32 [N,H,W], the ids of frame a at
+    level 0 (ia is level `level` of it): no smoothness couples two ids."""
     p = refine_params(dict(alpha=alpha, delta=delta, gamma=gamma, outer=outer, sor=sor, omega=omega))
     ia, ib, flow = _level_inputs(ia, ib, flow)
     N, h, w = ia.shape
+    segments = _segment_ids(segments, N, h, w, level, ia.device)
     if out is None:
         out = torch.empty_like(flow)
     elif out.data_ptr() == flow.data_ptr():
         raise ValueError("refine_flow: out must not be the input flow (a tile reads its neighbours' input)")
-    return _refine_level(ia, ib, flow, p, _refine_workspace(N, h, w, ia.device), out)
+    return _refine_level(ia, ib, flow, p, _refine_workspace(N, h, w, ia.device), out, segments=segments, level=level)
 
 
-def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine=None):
+def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine=None, segments=None):
     """Flow a -> b of N image pairs -> [N,2,H,W] fp32 pixels (channel 0 = x; a(x) ~ b(x + flow(x))).
 
     a, b [N,3,H,W] fp32 or bf16 on the device, H, W >= 8, values in value_range = (lo, hi).  levels: at most that many pyramid
@@ -226,10 +271,18 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine
     level 0 by 2 * f[y // 2, x // 2] per level.  iters: search steps per patch and level, the same for every patch.
     refine: None / False: the densified patch flow; True: the variational refinement of DESIGN.md 4.2m after the densify of
     every searched level, with REFINE_DEFAULTS; a dict overrides those (see refine_params).
+    segments: None, or the int32 ids [N,H,W] of frame a (instance ids; any integer is an id): the patch sums, the average over
+    patches and the refinement's smoothness stop at id borders, which keeps the motion edge of an object sharp (DESIGN.md 4.2p;
+    the same number of launches).  One id everywhere gives the bits of segments=None.
     1 + 2 * (levels - finest) launches on the current stream whatever N is (1 + (3 + outer) * (levels - finest) with refinement),
     no synchronisation, no copy to the host; the result is bit-repeatable and that of a pair does not depend on the other pairs
     of the call.  No gradient flows through it."""
     rp = refine_params(refine)
+    if segments is not None:
+        N, H, W = _pair(a, b)
+        segments = _segment_ids(segments, N, H, W, 0, a.device)
+        if tuple(segments.shape) != (N, H, W):
+            raise ValueError(f"segments must be an int32 {[N, H, W]} tensor, got {list(segments.shape)}")
     with torch.no_grad():
         work, sizes, images = flow_pyramid(a, b, value_range, levels)
         N, (H, W), n = a.shape[0], sizes[0], len(sizes)
@@ -242,24 +295,32 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine
         rec0 = L.c2m_flow_workspace_offset(N, H, W, n, 3, 0)
         out = torch.empty(N, 2, H, W, device=a.device, dtype=torch.float32)
         flow = None
+        guide = {}
+        if segments is not None:                                      # records of 4 floats: a buffer of their own
+            hf, wf = sizes[finest]
+            grec = torch.empty(4 * N * len(patch_origins(hf)) * len(patch_origins(wf)), device=a.device)
         if rp is not None:                                            # the refinement's own buffers, sized for the finest level
             hf, wf = sizes[finest]
             rwork, patchflow = _refine_workspace(N, hf, wf, a.device), torch.empty(2 * N * hf * wf, device=a.device)
         for l in range(n - 1, finest - 1, -1):
             (h, w), (ia, ib) = sizes[l], images[l]
             npy, npx = len(patch_origins(h)), len(patch_origins(w))
-            rec = patch_search(ia, ib, flow, iters, out=work[rec0:rec0 + N * npy * npx * 3].view(N, npy, npx, 3))
+            if segments is None:
+                rec = work[rec0:rec0 + N * npy * npx * 3].view(N, npy, npx, 3)
+            else:
+                rec, guide = grec[:N * npy * npx * 4].view(N, npy, npx, 4), dict(segments=segments, level=l)
+            rec = patch_search(ia, ib, flow, iters, out=rec, **guide)
             if rp is not None:                                        # densify -> refine -> the place the plain flow would go to
-                dense = densify(ia, ib, rec, out=patchflow[:2 * N * h * w].view(N, 2, h, w))
+                dense = densify(ia, ib, rec, out=patchflow[:2 * N * h * w].view(N, 2, h, w), **guide)
                 if l == finest:
-                    return _refine_level(ia, ib, dense, rp, rwork, out, shift=l)
+                    return _refine_level(ia, ib, dense, rp, rwork, out, shift=l, **guide)
                 o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)
-                flow = _refine_level(ia, ib, dense, rp, rwork, work[o:o + 2 * N * h * w].view(N, 2, h, w))
+                flow = _refine_level(ia, ib, dense, rp, rwork, work[o:o + 2 * N * h * w].view(N, 2, h, w), **guide)
                 continue
             if l == finest:
-                return densify(ia, ib, rec, shift=l, out_size=(H, W), out=out)
+                return densify(ia, ib, rec, shift=l, out_size=(H, W), out=out, **guide)
             o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)
-            flow = densify(ia, ib, rec, out=work[o:o + 2 * N * h * w].view(N, 2, h, w))
+            flow = densify(ia, ib, rec, out=work[o:o + 2 * N * h * w].view(N, 2, h, w), **guide)
 
 
 def chain_flows(steps, order="backward", return_valid=False):
@@ -292,7 +353,7 @@ def chain_flows(steps, order="backward", return_valid=False):
     return (out, valid) if return_valid else out
 
 
-def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, value_range=(0, 1), **dense_flow_kw):
+def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, value_range=(0, 1), segments=None, **dense_flow_kw):
     """The dict of train.compute_flow for video [B,3,T,H,W] (T >= t_in + t_out; values in value_range), with the flows between
     the last input frame and the predicted frames CHAINED through the frames in between instead of searched across up to t_out
     frames: `target_bw_of` [B,2,t_out,H,W] is the backward chain from the last input frame, `target_bw_occ` [B,1,t_out,H,W] is
@@ -300,7 +361,9 @@ def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, v
     the backward one.  `input_of` / `input_occ` (None for t_in = 1) are the consecutive flows themselves, as compute_flow has
     them, and so is the first target frame.  ONE dense_flow call over the 2 (t_in - 1 + t_out) B consecutive pairs (both
     directions; dense_flow_kw: levels, finest, iters, refine), two chain launches, the splats and the copies that bring the
-    results into compute_flow's layout: a number of launches that does not depend on B."""
+    results into compute_flow's layout: a number of launches that does not depend on B.
+    segments: the int32 ids [B,T,H,W] of every frame of the video: the pair (c_j -> c_j+1) is guided by the ids of frame j, the
+    pair (c_j+1 -> c_j) by those of frame j + 1 (dense_flow's `segments`, still ONE call)."""
     t_in, t_out = int(num_input_frames), int(num_predicted_frames)
     if t_in < 1 or not 1 <= t_out <= CHAIN_CAP:
         raise ValueError(f"clip_flows needs num_input_frames >= 1 and 1 <= num_predicted_frames <= {CHAIN_CAP}, got {t_in}, {t_out}")
@@ -308,9 +371,19 @@ def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, v
         raise ValueError(f"video must be a [B,3,T,H,W] tensor with T >= {t_in + t_out}, got {list(getattr(video, 'shape', ()))}")
     B, _, _, H, W = video.shape
     n, n_in = t_in + t_out - 1, t_in - 1                              # consecutive pairs of a clip; those between input frames
+    if segments is not None:
+        if not isinstance(segments, torch.Tensor) or segments.dtype != torch.int32 or segments.dim() != 4 or \
+                segments.shape[0] != B or segments.shape[1] < n + 1 or tuple(segments.shape[2:]) != (H, W):
+            raise ValueError(f"segments must be an int32 [B,T,H,W] tensor with the video's B, H, W and T >= {n + 1}, got "
+                             f"{getattr(segments, 'dtype', None)} {list(getattr(segments, 'shape', ()))}")
+        if segments.device != video.device:
+            raise ValueError(f"segments must be on the device of the video ({video.device}), got {segments.device}")
     with torch.no_grad():
         frames = video.detach()[:, :, :n + 1].transpose(1, 2)         # [B,T,3,H,W]
         f0, f1 = frames[:, :-1].reshape(B * n, 3, H, W), frames[:, 1:].reshape(B * n, 3, H, W)
+        if segments is not None:                                      # the ids of the first frame of every pair
+            ids = segments.detach()[:, :n + 1]
+            dense_flow_kw["segments"] = torch.cat([ids[:, :-1].reshape(B * n, H, W), ids[:, 1:].reshape(B * n, H, W)])
         flows = dense_flow(torch.cat([f0, f1]), torch.cat([f1, f0]), value_range, **dense_flow_kw).view(2, B, n, 2, H, W)
         fw, bw = flows[0], flows[1]                                   # [:, j]: c_j -> c_{j+1} and c_{j+1} -> c_j
         fw_chain, bw_chain = chain_flows(fw[:, n_in:], "forward"), chain_flows(bw[:, n_in:], "backward")
@@ -330,7 +403,11 @@ class ClassicFlow(nn.Module):
     where train.compute_flow puts the frames; ClassicFlow(value_range=(0, 1)).compute_flow_and_conf is the `flow_fn` of
     interactive.rollout.  refine: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8.
     chain=True: train.compute_flow takes its targets from `clip_flows` (the consecutive flows of the clip, chained) instead of
-    searching each (last input frame, predicted frame) pair directly; the call surface above is the same either way."""
+    searching each (last input frame, predicted frame) pair directly; the call surface above is the same either way.
+    segments: forward, compute_flow_and_conf and clip_flows take the int32 ids of the first frame of every pair (of every frame
+    of the clip) and pass them to dense_flow; train.compute_flow(..., segments=) hands them over."""
+
+    takes_segments = True                                             # train.compute_flow asks before it passes `segments`
 
     def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None, chain=False):
         super().__init__()
@@ -338,24 +415,30 @@ class ClassicFlow(nn.Module):
         refine_params(refine)                                         # a bad parameter raises here, not at the first call
         self.refine, self.chain = refine, bool(chain)
 
-    def clip_flows(self, train_batch, train_params):
-        """train.compute_flow's dict for a batch, by `clip_flows`; the frames go to [-1, 1] first, as compute_flow puts them."""
+    def clip_flows(self, train_batch, train_params, segments=None):
+        """train.compute_flow's dict for a batch, by `clip_flows`; the frames go to [-1, 1] first, as compute_flow puts them.
+        segments: the int32 ids [B,T,H,W] of every frame."""
         return clip_flows(train_batch["video"] * 2 - 1, train_params["num_input_frames"], train_params["num_predicted_frames"],
                           train_params.get("use_fw_of", False), self.value_range, levels=self.levels, finest=self.finest,
-                          iters=self.iters, refine=self.refine)
+                          iters=self.iters, refine=self.refine, **({} if segments is None else dict(segments=segments)))
 
-    def forward(self, input_A, input_B):
+    def forward(self, input_A, input_B, segments=None):
         size = input_A.size()
         if len(size) not in (4, 5, 6):
             raise ValueError(f"ClassicFlow takes [N,3,H,W], [b,n,3,H,W] or [b,t,n,3,H,W], got {list(size)}")
+        if segments is not None and (not isinstance(segments, torch.Tensor) or
+                                     tuple(segments.shape) != tuple(size[:-3]) + tuple(size[-2:])):
+            raise ValueError(f"segments must be an int32 {list(size[:-3]) + list(size[-2:])} tensor (the ids of input_A), got "
+                             f"{list(getattr(segments, 'shape', ()))}")
         if len(size) == 4:
-            return self.compute_flow_and_conf(input_A, input_B)
+            return self.compute_flow_and_conf(input_A, input_B, segments)
         c, h, w = size[-3:]
-        flow, conf = self.compute_flow_and_conf(input_A.contiguous().view(-1, c, h, w), input_B.contiguous().view(-1, c, h, w))
+        flow, conf = self.compute_flow_and_conf(input_A.contiguous().view(-1, c, h, w), input_B.contiguous().view(-1, c, h, w),
+                                                None if segments is None else segments.contiguous().view(-1, h, w))
         return flow.view(*size[:-3], 2, h, w), conf.view(*size[:-3], 1, h, w)
 
-    def compute_flow_and_conf(self, im1, im2):
-        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters, self.refine)
+    def compute_flow_and_conf(self, im1, im2, segments=None):
+        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters, self.refine, segments)
         with torch.no_grad():
             conf = ops.occlusion_splat(flow)[0]
         return flow, conf

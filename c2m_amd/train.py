@@ -28,7 +28,7 @@ def init_distributed():
     return int(os.environ.get("RANK", "0")), local_rank, world
 
 
-def compute_flow(flownet, train_batch, train_params):
+def compute_flow(flownet, train_batch, train_params, segments=None):
     """Trainer.compute_flow (src/trainer/trainer.py:42-98): optical flow + occlusion targets from the frozen flow net when
     `use_pre_processed_of` is False.  Forward flow between consecutive input frames -> `input_of` / `input_occ` (the
     occlusion comes from the reverse pair); between the last input frame and every predicted frame both directions ->
@@ -36,12 +36,24 @@ def compute_flow(flownet, train_batch, train_params):
     The 2 * (t_in - 1 + t_out) flow-net passes of the reference loop are issued as ONE batched pass: the pairs are
     independent images and every kernel of the net is batch-wise bit-deterministic.
     A flow module with a true `chain` attribute (flow.ClassicFlow(chain=True)) returns the same dict from its own `clip_flows`:
-    the flows between consecutive frames, chained across the gap."""
-    if getattr(flownet, "chain", False):
-        return flownet.clip_flows(train_batch, train_params)
+    the flows between consecutive frames, chained across the gap.
+    segments: the int32 instance ids [B,T,H,W] of every frame, for a flow module that takes them (flow.ClassicFlow; DESIGN.md
+    4.2p): every pair is guided by the ids of its first frame.  A module that cannot (FlowNet) raises ValueError."""
+    if segments is not None and not getattr(flownet, "takes_segments", False):
+        raise ValueError(f"compute_flow: {type(flownet).__name__} takes no segments (flow.ClassicFlow does)")
     t_in, t_out = train_params["num_input_frames"], train_params["num_predicted_frames"]
     video = train_batch["video"]
     b = video.shape[0]
+    if segments is not None:                             # before anything is launched
+        if not isinstance(segments, torch.Tensor) or segments.dtype != torch.int32 or segments.dim() != 4 or \
+                segments.shape[0] != b or segments.shape[1] < t_in + t_out or segments.shape[2:] != video.shape[3:]:
+            raise ValueError(f"segments must be an int32 [B,T,H,W] tensor with the video's B, H, W and T >= {t_in + t_out}, got "
+                             f"{getattr(segments, 'dtype', None)} {list(getattr(segments, 'shape', ()))}")
+        if segments.device != video.device:
+            raise ValueError(f"segments must be on the device of the video ({video.device}), got {segments.device}")
+    if getattr(flownet, "chain", False):
+        return flownet.clip_flows(train_batch, train_params) if segments is None else \
+            flownet.clip_flows(train_batch, train_params, segments)
     frame = lambda i: video[:, :, i] * 2 - 1
     pairs = []                                           # (a, b) frame indices: flow a -> b, occlusion map of that flow
     for i in range(t_in - 1):
@@ -50,7 +62,10 @@ def compute_flow(flownet, train_batch, train_params):
         pairs += [(t_in - 1, t_in + i), (t_in + i, t_in - 1)]
     A = torch.cat([frame(a) for a, _ in pairs], 0)
     B = torch.cat([frame(c) for _, c in pairs], 0)
-    flow, conf = flownet(A, B)
+    if segments is None:
+        flow, conf = flownet(A, B)
+    else:
+        flow, conf = flownet(A, B, segments=torch.cat([segments[:, a] for a, _ in pairs], 0))
     flow = [f.unsqueeze(2) for f in flow.split(b)]
     conf = [c.unsqueeze(2) for c in conf.split(b)]
     n_in = t_in - 1

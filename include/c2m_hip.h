@@ -433,6 +433,30 @@ int c2m_flow_refine_iterate(const float* flow, long flow_elems, void* workspace,
                             int iteration, int sor, float alpha, float delta, float gamma, float omega, float* out,
                             long out_elems, int shift, int Ho, int Wo, void* stream);
 
+/* ---- segment-guided dense flow (dense_flow.hip, flow_refine.hip): c2m_amd.flow.dense_flow(segments=...) ---------------------
+ * The reference has no counterpart.  The three launchers above with a guide: segments [N][H][W] int32 (segment_elems of them),
+ * the ids of frame a at level 0; any integer is an id and none is special.  A stage on level `level` (0 .. 6) reads the id of
+ * its pixel (y, x) at segments[y << level][x << level]; ((h - 1) << level) < H and ((w - 1) << level) < W.  DESIGN.md 4.2p.
+ * c2m_flow_patch_search_guided: every patch sum runs over the n >= 1 pixels whose id is that of the patch centre (oy + 3,
+ *   ox + 3), means are sum / n, a patch is searched iff det > 40.96 * n^2 / 4096; records [N][npy][npx][4] = (u, v, mean(J) -
+ *   mean(T), n): record_elems >= 4 * N * npy * npx.
+ * c2m_flow_densify_guided: records of 4 floats; a pixel is averaged over the covering patches whose centre has its id (all of
+ *   them if there is none), weight n / max(1, |residual|).
+ * c2m_flow_refine_iterate_guided: a forward difference toward a neighbour of another id is 0 in the smoothness weight, and the
+ *   weight of an edge between two ids is 0.
+ * Everything else, the checks included, is as above; N == 0 returns 0.  With one id everywhere the results are those of the
+ * unguided launchers, bit for bit.                                                                                              */
+int c2m_flow_patch_search_guided(const float* ia, const float* ib, long image_elems, const float* init, long init_elems,
+                                 int init_shift, float* records, long record_elems, int N, int h, int w, int iters,
+                                 const int32_t* segments, long segment_elems, int level, int H, int W, void* stream);
+int c2m_flow_densify_guided(const float* ia, const float* ib, long image_elems, const float* records, long record_elems,
+                            float* flow, long flow_elems, int N, int h, int w, int shift, int Ho, int Wo,
+                            const int32_t* segments, long segment_elems, int level, int H, int W, void* stream);
+int c2m_flow_refine_iterate_guided(const float* flow, long flow_elems, void* workspace, long workspace_bytes, int N, int h,
+                                   int w, int iteration, int sor, float alpha, float delta, float gamma, float omega,
+                                   float* out, long out_elems, int shift, int Ho, int Wo, const int32_t* segments,
+                                   long segment_elems, int level, int H, int W, void* stream);
+
 /* ---- chains of frame-to-frame flows (flow_chain.hip): c2m_amd.flow.chain_flows, clip_flows ---------------------------------
  * The reference has no counterpart.  Frames c_0 .. c_K of N clips; steps [N][K][2][H][W] fp32, channel 0 = x, pixels, with the
  * convention above; out [N][K][2][H][W]; valid [N][K][H][W] uint8 or NULL.  DESIGN.md 4.2n states the algorithm.
