@@ -449,6 +449,46 @@ def _choose_ck(C, taps):
     return best[1]
 
 
+class _Layer(collections.namedtuple("_Layer", "N Cin Cout Ti Hi Wi To Ho Wo kt kh kw st sh sw pt ph pw nd reflect bf16 dM in_sc osp taps")):
+    """The numbers of one layer, as _ConvPlan.__init__ works them out: what the stages of a plan and the routing rules below read.
+    dM: rows of the data-gradient GEMM; in_sc / osp: elements of one input / output channel; taps = kt * kh * kw.  The three
+    kernel shapes with kernels of their own: 3x3 stride 1 pad 1; 4x4 stride 2 pad 1 on even extents; 3x3x3 stride 1 pad 1."""
+    __slots__ = ()
+    k = property(lambda ly: (ly.kt, ly.kh, ly.kw))
+    stride = property(lambda ly: (ly.st, ly.sh, ly.sw))
+    is_3x3_s1p1 = property(lambda ly: ly.k == (1, 3, 3) and ly.stride == (1, 1, 1) and (ly.ph, ly.pw) == (1, 1))
+    is_4x4_s2p1_even = property(lambda ly: ly.k == (1, 4, 4) and ly.stride == (1, 2, 2) and (ly.ph, ly.pw) == (1, 1) and
+                                ly.Hi % 2 == 0 and ly.Wi % 2 == 0)
+    is_333_s1p1 = property(lambda ly: ly.k == (3, 3, 3) and ly.stride == (1, 1, 1) and (ly.pt, ly.ph, ly.pw) == (1, 1, 1))
+
+
+def _rows_ok(m):
+    """Rows of a Winograd forward / data gradient: 64-row tiles need >= 48 output channels to pay; 17..32 run on the 32-row variant
+    (MT = 1, three workgroups per CU), which beats the direct kernels' 32-row tiles."""
+    return m >= 48 or 17 <= m <= 32
+
+
+def _wino_gate(regions, pixels, fit, K, M):
+    """A Winograd forward / data gradient of M rows over a K-deep reduction pays: the domain's `pixels` fill at least `fit` of its
+    `regions` (128 outputs each), and the grid is big enough."""
+    return _WINO == "force" or (_WINO == "auto" and pixels >= fit * regions * 128 and K >= 32 and _rows_ok(M) and
+                                regions * _cdiv(M, 64) >= _WINO_MIN_WGS)
+
+
+def _chan16_ok(c, limit):
+    """c channels as whole 16-channel chunks: at least 12, padded to at most `limit` times their number."""
+    return c >= 12 and _ceil(c, 16) <= limit * c
+
+
+def _tile_area(H, W, rows=8):
+    return _ceil(W, 32) * _ceil(H, rows)
+
+
+def _fill_ok(H, W, limit, rows=8):
+    """The (rows x 32) tiles of an H x W domain cover at most `limit` times its pixels."""
+    return _tile_area(H, W, rows) <= limit * W * H
+
+
 def _patch_ok(C, taps3, stride, splits, Ho, Wo, M):
     """LDS-patch kernel eligibility: 3x3 (kt = 1) stride-1, whole 16-channel chunks without much padding, a grid big
     enough not to need split-K, output rows/cols that fill the (rows x 32) tile reasonably."""
@@ -459,7 +499,7 @@ def _patch_ok(C, taps3, stride, splits, Ho, Wo, M):
     if _ceil(C, 16) > 1.10 * best:
         return False
     rows = 8 if M <= 32 else 4
-    return Wo >= 32 and Ho >= rows and (_ceil(Wo, 32) * _ceil(Ho, rows)) <= 1.15 * Wo * Ho
+    return Wo >= 32 and Ho >= rows and _fill_ok(Ho, Wo, 1.15, rows)
 
 
 def _patch_bf16_ok(C, stride, Ho, Wo, M, fill_limit=None, nc8=True):
@@ -467,9 +507,9 @@ def _patch_bf16_ok(C, stride, Ho, Wo, M, fill_limit=None, nc8=True):
     (per-shape A/B of BASELINE configs[2], gpurun_out/r02/table_cfg2*.txt): deep reductions (>= 128 channels: the weight
     image of a chunk is re-streamed per 256 pixels, which only pays with many chunks) or few output rows (<= 64), and
     tiles that do not hang far over the (padded) domain; <= 4 output rows stay on the vector-ALU kernels."""
-    if tuple(stride) != (1, 1, 1) or M <= 4 or C < 12 or Wo < 32 or Ho < 8 or _ceil(C, 16) > 1.25 * C:
+    if tuple(stride) != (1, 1, 1) or M <= 4 or Wo < 32 or Ho < 8 or not _chan16_ok(C, 1.25):
         return False
-    fill = (_ceil(Wo, 32) * _ceil(Ho, 8)) / float(Wo * Ho)
+    fill = _tile_area(Ho, Wo) / float(Wo * Ho)      # (the quotient, not _fill_ok's product: the two round differently)
     if _NC8 and nc8:      # the channel-blocked kernel (conv_nc8.hip) has no 2-byte gathers to amortise: every layer whose tiles fit
                           # (nc8: the plan can run it -- planes of whole 8-pixel groups; otherwise the NCHW kernel's own rule below, ADVICE r04)
         return fill <= (fill_limit or _NC8_FILL)      # (the padded 34x66 domain of a reflect data gradient fills 58 % of its tiles: still 1.5x the gather kernel)
@@ -732,7 +772,8 @@ def _geom(**kw):
     idx = dict(M=G.M, nk=G.NK, lda=G.LDA, Npix=G.NPIX, To=G.TO, Ho=G.HO, Wo=G.WO, Ti=G.TI, Hi=G.HI, Wi=G.WI, st=G.ST, sh=G.SH, sw=G.SW,
                in_sn=G.IN_SN, in_st=G.IN_ST, in_sh=G.IN_SH, out_sn=G.OUT_SN, out_sc=G.OUT_SC, out_st=G.OUT_ST, out_sh=G.OUT_SH,
                out_sw=G.OUT_SW, out_off=G.OUT_OFF, reflect=G.REFLECT, is3d=G.IS3D, ns=G.NS, in_sc=G.IN_SC, splits=G.SPLITS,
-               slab_stride=G.SLAB_STRIDE, Cin=G.CIN, taps=G.TAPS, ntg=G.NTG, ngroups=G.NGROUPS, x_bytes=G.X_BYTES, dy_bytes=G.DY_BYTES)
+               slab_stride=G.SLAB_STRIDE, Cin=G.CIN, taps=G.TAPS, ntg=G.NTG, ngroups=G.NGROUPS, x_bytes=G.X_BYTES, dy_bytes=G.DY_BYTES,
+               precision=G.PRECISION)
     for k, v in kw.items():
         g[idx[k]] = v
     return g
@@ -781,13 +822,21 @@ def _ring_pack(w, Cout, Cin):
     return A
 
 
-def _wino_geom(head, To=0, in_st=0, out_st=0, cin=0, nkt=0, toff=0, Ti=0, treflect=0):
-    """geom[] of c2m_conv_wino (include/c2m_hip.h): 33 entries; the tail describes the time taps of a 3x3x3 layer."""
+def _wino_geom(**kw):
+    """geom[] of c2m_conv_wino from its entries by name (C2M_WG_* of include/c2m_geom.h in lower case; what is not named is 0):
+    m rows, k reduction depth, nimg images; hi, wi / ho, wo: input / output extents, with strides in_sn, in_sc, in_sh / out_sn, out_sc,
+    out_sh; iy0, ix0: input origin of output (0, 0); reflect; x_bytes: byte bound of the input.  Two-target epilogue (_wino_interior):
+    y2_* strides, lo_* origin and ext_* extents of the interior.  3x3x3 layers: to frames, in_st / out_st, cin x nkt virtual channels,
+    toff, ti input frames, treflect."""
     g = np.zeros(WG.LEN, dtype=np.int64)
-    assert len(head) in (WG.X_BYTES + 1, WG.EXT_X + 1)       # M .. X_BYTES in enum order (+ the Y_interior block Y2_SN .. EXT_X)
-    g[:len(head)] = head
-    g[WG.TO:WG.TREFLECT + 1] = (To, in_st, out_st, cin, nkt, toff, Ti, treflect)
+    for k, v in kw.items():
+        g[WG[k.upper()]] = v
     return g
+
+
+def _wino_interior(ly):
+    """Two-target block of a reflect data gradient's Winograd geom: the pad-1 interior of the launched domain goes straight into dX."""
+    return dict(y2_sn=ly.Cin * ly.in_sc, y2_sc=ly.in_sc, y2_sh=ly.Wi, lo_y=1, lo_x=1, ext_y=ly.Hi, ext_x=ly.Wi)
 
 
 def _time_pair_table(T):
@@ -817,7 +866,7 @@ class _ConvPlan:
         L = _lib.lib()
         self.bf16 = bf16
         nd = len(xs) - 2
-        self.is3d = is3d = 1 if nd == 3 else 0
+        self.is3d = 1 if nd == 3 else 0
         N, Cin = xs[0], xs[1]
         if ws[1] != Cin:
             # torch.nn.functional.conv2d raises here too.  Without the check the pack kernels read Cin * taps weights per output
@@ -848,190 +897,209 @@ class _ConvPlan:
         dM = self.dM = int(dgrad_rows) if dgrad_rows and tuple(stride) == (1, 1, 1) and 0 < dgrad_rows < Cin else Cin
         self.stride, self.pad, self.reflect = stride, pad, reflect
         self.out_shape = (N, Cout, To, Ho, Wo) if nd == 3 else (N, Cout, Ho, Wo)
-        taps = kt * kh * kw
-        self.K = Cin * taps
-        in_sc, osp = Ti * Hi * Wi, To * Ho * Wo
-        # ---- Winograd F(2x2,3x3) for the 3x3 stride-1 2-D layers (fp32 mode): forward, and the data gradient when the
-        # padding is zeros (the reflect data gradient runs over the padded domain with the two-target epilogue)
-        self.wino_fwd = self.wino_dgrad = self.wino_wgrad = self.ring_dgrad = False
-        # rows: 64-row tiles need >= 48 output channels to pay; 17..32 run on the 32-row variant (MT = 1, three
-        # workgroups per CU), which beats the direct kernels' 32-row tiles
-        rows_ok = lambda m: m >= 48 or 17 <= m <= 32
+        self.K = Cin * kt * kh * kw
+        ly = _Layer(N, Cin, Cout, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, pt, ph, pw, nd, reflect, bf16, dM,
+                    Ti * Hi * Wi, To * Ho * Wo, kt * kh * kw)
+        self._plan_wino2d(ly, L)
+        self._plan_wino3d(ly, L, device)
+        self._plan_nc8(ly, device)
+        offs = self._plan_forward(ly, L, device)
+        self._plan_wgrad(ly, L, offs, device)
+        self._plan_dgrad_classes(ly, L, device)
+        self._plan_class_batching(ly, L)
+        self._plan_g8(ly, offs, device)
+        self._plan_routes()
+        self._plan_call_constants(ly)
 
-        def wino_wgrad_pays(Kw, nimg):         # Winograd weight gradient over Kw input channels (3-D: virtual (kt, ci)) and nimg images
-            wrows = 32 if Cout <= 32 else 64                      # workgroup tile: 64 (32 for Cout <= 32) output x 32 input channels
-            wg_tiles = _cdiv(Kw, 32) * _cdiv(Cout, wrows)
-            # A/B against the direct kernel (tools/ab_wino_wgrad.py, AB_EXTRA=1 for the marginal shapes): the Winograd form
-            # wins 1.1-1.3x even on a half-empty 64-row tile as long as there are two tiles
-            waste = 32.0 * wrows * wg_tiles / (Kw * Cout)
-            if not (Hi % 2 == 0 and Wi % 16 == 0 and (Kw * Cout) % 4 == 0 and (_WINO_WGRAD == "force" or (
-                    _WINO_WGRAD == "auto" and (waste <= 1.35 or (waste <= 2.0 and wg_tiles >= 2))
-                    and nimg * (Hi // 2) * (Wi // 16) >= 8 * max(1, (768 if wrows == 32 else 512) // wg_tiles)))):
-                return False
-            self.wino_wg_splits = L.c2m_wino_wgrad_splits(Cout, Kw, nimg, Hi, Wi)
-            return True
+    def _fwd_on_patch_nc8(self):
+        return self.fwd_patch and self.nc8
+
+    def _dgrad_on_patch_nc8(self):
+        """The single 3x3 stride-1 class of a bf16 layer whose dY planes are whole 8-pixel groups (a patch class is the only class)."""
+        return bool(self.bf16 and _NC8 and self.classes and all(c["patch"] for c in self.classes) and not self.is3d and
+                    (self.dims[7] * self.dims[8]) % 8 == 0)
+
+    def _wino_wgrad_pays(self, ly, L, Kw, nimg):
+        """Winograd weight gradient over Kw input channels (3-D: virtual (kt, ci)) and nimg images.  Sets wino_wg_splits where it pays."""
+        Cout, Hi, Wi = ly.Cout, ly.Hi, ly.Wi
+        wrows = 32 if Cout <= 32 else 64                      # workgroup tile: 64 (32 for Cout <= 32) output x 32 input channels
+        wg_tiles = _cdiv(Kw, 32) * _cdiv(Cout, wrows)
+        # A/B against the direct kernel (tools/ab_wino_wgrad.py, AB_EXTRA=1 for the marginal shapes): the Winograd form
+        # wins 1.1-1.3x even on a half-empty 64-row tile as long as there are two tiles
+        waste = 32.0 * wrows * wg_tiles / (Kw * Cout)
+        if not (Hi % 2 == 0 and Wi % 16 == 0 and (Kw * Cout) % 4 == 0 and (_WINO_WGRAD == "force" or (
+                _WINO_WGRAD == "auto" and (waste <= 1.35 or (waste <= 2.0 and wg_tiles >= 2))
+                and nimg * (Hi // 2) * (Wi // 16) >= 8 * max(1, (768 if wrows == 32 else 512) // wg_tiles)))):
+            return False
+        self.wino_wg_splits = L.c2m_wino_wgrad_splits(Cout, Kw, nimg, Hi, Wi)
+        return True
+
+    def _plan_wino2d(self, ly, L):
+        """Winograd F(2x2,3x3) / F(4x4,3x3) for the 3x3 stride-1 pad-1 2-D layers (fp32 mode): forward, weight gradient and data
+        gradient.  Data gradient: zero padding -> the unpadded domain; reflect padding -> EITHER the exact H x W domain (the interior
+        of the padded gradient = the zero-padded "same" data gradient, full Winograd regions) + the pad ring folded into dX
+        by c2m_reflect_ring_dgrad (conv_ring.hip: four thin GEMMs, 3/9 (2H+2W)/(HW) of the layer's FLOPs -- maps of
+        >= _RING_MIN_PIX pixels), OR the padded (H+2)x(W+2) domain with the two-target epilogue (interior straight into dX,
+        pad ring into a scratch tensor that is then folded).
+        Sets: wino_fwd, wino_dgrad, wino_wgrad, ring_dgrad, wino4_fwd, wino4_dgrad (all False unless the layer qualifies);
+        wino_fwd_geom, wino_dgrad_geom, wino_wg_splits where their flag is set.  Reads: the layer only."""
+        N, Cin, Cout, Hi, Wi, Ho, Wo, reflect, in_sc, osp = ly.N, ly.Cin, ly.Cout, ly.Hi, ly.Wi, ly.Ho, ly.Wo, ly.reflect, ly.in_sc, ly.osp
+        self.wino_fwd = self.wino_dgrad = self.wino_wgrad = self.ring_dgrad = False
         self.wino4_fwd = self.wino4_dgrad = False         # F(4x4,3x3) instead of F(2x2,3x3) for that launch (2-D layers)
-        if not bf16 and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and (ph, pw) == (1, 1) and nd == 2:
-            self.wino_wgrad = wino_wgrad_pays(Cin, N)
-            # regions per image: 8 x 16 outputs, or the th x tw tile shape c2m_conv_wino picks for a badly fitting domain
-            regions = N * L.c2m_wino_regions(Ho, Wo)
-            fit = N * Ho * Wo >= 0.8 * regions * 128
-            if _WINO == "force" or (_WINO == "auto" and fit and Cin >= 32 and rows_ok(Cout) and
-                                    regions * _cdiv(Cout, 64) >= _WINO_MIN_WGS):
-                self.wino_fwd = True
-                self.wino_fwd_geom = _wino_geom([Cout, Cin, N, Hi, Wi, Ho, Wo, -1, -1, int(reflect), Cin * in_sc, in_sc, Wi,
-                                                 Cout * osp, osp, Wo, 0, 4 * N * Cin * in_sc])
-                self.wino4_fwd = _wino4_pays(L, Cout, Cin, N, Ho, Wo)
-            # data gradient: zero padding -> the unpadded domain; reflect padding -> EITHER the exact H x W domain (the interior
-            # of the padded gradient = the zero-padded "same" data gradient, full Winograd regions) + the pad ring folded into dX
-            # by c2m_reflect_ring_dgrad (conv_ring.hip: four thin GEMMs, 3/9 (2H+2W)/(HW) of the layer's FLOPs -- maps of
-            # >= _RING_MIN_PIX pixels), OR the padded (H+2)x(W+2) domain with the two-target epilogue (interior straight into dX,
-            # pad ring into a scratch tensor that is then folded)
-            if reflect and dM == Cin and _RING != "off" and Hi >= 4 and Wi >= 4 and (_RING == "force" or Hi * Wi >= _RING_MIN_PIX):
-                eregions = N * L.c2m_wino_regions(Hi, Wi)
-                efit = N * Hi * Wi >= 0.8 * eregions * 128
-                w4e = _wino4_pays(L, Cin, Cout, N, Hi, Wi)
-                # measured per shape in the step (profiles/r05_ab_ring_*): the route pays where the exact domain moves the layer to
-                # F(4x4) (1.3-1.65x) and on the <= 32 x 64 maps whose padded domain wastes a third of the F(2x2) regions (1.14-1.26x);
-                # F(2x2) layers on >= 64 x 128 maps (padded fill 0.8-0.9) gain less than the ring launch costs
-                pays = _RING == "force" or w4e or Hi * Wi <= _RING_F2_MAX_PIX
-                if pays and (_WINO == "force" or (_WINO == "auto" and efit and Cout >= 32 and rows_ok(Cin) and
-                                                  eregions * _cdiv(Cin, 64) >= _WINO_MIN_WGS)):
-                    self.wino_dgrad = self.ring_dgrad = True
-                    self.wino_dgrad_geom = _wino_geom(
-                        [Cin, Cout, N, Ho, Wo, Hi, Wi, -1, -1, 0, Cout * osp, osp, Wo, Cin * in_sc, in_sc, Wi, 0, 4 * N * Cout * osp])
-                    self.wino4_dgrad = w4e
-            Hd, Wd = (Hi + 2, Wi + 2) if reflect else (Hi, Wi)
-            dregions = N * L.c2m_wino_regions(Hd, Wd)
-            dfit = N * Hd * Wd >= _WINO_DFIT * dregions * 128
-            if not self.ring_dgrad and dM == Cin and (_WINO == "force" or (_WINO == "auto" and dfit and Cout >= 32 and rows_ok(Cin) and
-                                                                         dregions * _cdiv(Cin, 64) >= _WINO_MIN_WGS)):
-                self.wino_dgrad = True
-                o = -2 if reflect else -1
-                self.wino_dgrad_geom = _wino_geom(
-                    [Cin, Cout, N, Ho, Wo, Hd, Wd, o, o, 0, Cout * osp, osp, Wo, Cin * Hd * Wd, Hd * Wd, Wd, 0,
-                     4 * N * Cout * osp, Cin * in_sc, in_sc, Wi, 1, 1, Hi, Wi])
-                self.wino4_dgrad = _wino4_pays(L, Cin, Cout, N, Hd, Wd)
-        # ---- 3x3x3 stride-1 pad-1 layers (fuse_convs, the 3-D blocks): a 2-D Winograd over virtual input channels
-        # (time tap, channel) with image = (sample, frame) -- the K loop is three times as deep as the 2-D layer's, the
-        # temporal padding is a per-tap frame index (reflected, or a zero-record descriptor).  Data gradient: virtual
-        # channels (flipped time tap, output channel) of dY over the padded (T+2, H+2, W+2) domain (reflect; then one
-        # fold pass) or the unpadded one (zeros).
+        if ly.bf16 or not ly.is_3x3_s1p1 or ly.nd != 2:
+            return
+        self.wino_wgrad = self._wino_wgrad_pays(ly, L, Cin, N)
+        # regions per image: 8 x 16 outputs, or the th x tw tile shape c2m_conv_wino picks for a badly fitting domain
+        if _wino_gate(N * L.c2m_wino_regions(Ho, Wo), N * Ho * Wo, 0.8, Cin, Cout):
+            self.wino_fwd = True
+            self.wino_fwd_geom = _wino_geom(m=Cout, k=Cin, nimg=N, hi=Hi, wi=Wi, ho=Ho, wo=Wo, iy0=-1, ix0=-1, reflect=int(reflect),
+                                            in_sn=Cin * in_sc, in_sc=in_sc, in_sh=Wi, out_sn=Cout * osp, out_sc=osp, out_sh=Wo,
+                                            x_bytes=4 * N * Cin * in_sc)
+            self.wino4_fwd = _wino4_pays(L, Cout, Cin, N, Ho, Wo)
+        dy = dict(m=Cin, k=Cout, nimg=N, hi=Ho, wi=Wo, in_sn=Cout * osp, in_sc=osp, in_sh=Wo, x_bytes=4 * N * Cout * osp)
+        if reflect and ly.dM == Cin and _RING != "off" and Hi >= 4 and Wi >= 4 and (_RING == "force" or Hi * Wi >= _RING_MIN_PIX):
+            w4e = _wino4_pays(L, Cin, Cout, N, Hi, Wi)
+            # measured per shape in the step (profiles/r05_ab_ring_*): the route pays where the exact domain moves the layer to
+            # F(4x4) (1.3-1.65x) and on the <= 32 x 64 maps whose padded domain wastes a third of the F(2x2) regions (1.14-1.26x);
+            # F(2x2) layers on >= 64 x 128 maps (padded fill 0.8-0.9) gain less than the ring launch costs
+            pays = _RING == "force" or w4e or Hi * Wi <= _RING_F2_MAX_PIX
+            if pays and _wino_gate(N * L.c2m_wino_regions(Hi, Wi), N * Hi * Wi, 0.8, Cout, Cin):
+                self.wino_dgrad = self.ring_dgrad = True
+                self.wino_dgrad_geom = _wino_geom(ho=Hi, wo=Wi, iy0=-1, ix0=-1, out_sn=Cin * in_sc, out_sc=in_sc, out_sh=Wi, **dy)
+                self.wino4_dgrad = w4e
+        Hd, Wd = (Hi + 2, Wi + 2) if reflect else (Hi, Wi)
+        if not self.ring_dgrad and ly.dM == Cin and _wino_gate(N * L.c2m_wino_regions(Hd, Wd), N * Hd * Wd, _WINO_DFIT, Cout, Cin):
+            self.wino_dgrad = True
+            o = -2 if reflect else -1
+            self.wino_dgrad_geom = _wino_geom(ho=Hd, wo=Wd, iy0=o, ix0=o, out_sn=Cin * Hd * Wd, out_sc=Hd * Wd, out_sh=Wd,
+                                              **dy, **_wino_interior(ly))
+            self.wino4_dgrad = _wino4_pays(L, Cin, Cout, N, Hd, Wd)
+
+    def _plan_wino3d(self, ly, L, device):
+        """3x3x3 stride-1 pad-1 layers (fuse_convs, the 3-D blocks; fp32 mode): a 2-D Winograd over virtual input channels
+        (time tap, channel) with image = (sample, frame) -- the K loop is three times as deep as the 2-D layer's, the
+        temporal padding is a per-tap frame index (reflected, or a zero-record descriptor).  Data gradient: virtual
+        channels (flipped time tap, output channel) of dY over the padded (T+2, H+2, W+2) domain (reflect; then one
+        fold pass) or the unpadded one (zeros).
+        Sets: wino3d, wino_wgrad3d, wino3d_pairs (always); wino_fwd, wino_dgrad, wino_wgrad, wino_fwd_geom, wino_dgrad_geom,
+        wino_dgrad_target, wino_pair_tab, wino_wg_splits where the layer qualifies.  Reads: the layer only."""
+        N, Cin, Cout, Ti, Hi, Wi, To, Ho, Wo, reflect, in_sc, osp = ly[:9] + (ly.reflect, ly.in_sc, ly.osp)
         self.wino3d = self.wino_wgrad3d = self.wino3d_pairs = False
-        if not bf16 and nd == 3 and (kt, kh, kw) == (3, 3, 3) and tuple(stride) == (1, 1, 1) and (pt, ph, pw) == (1, 1, 1):
-            regions = N * To * L.c2m_wino_regions(Ho, Wo)
-            fit = N * To * Ho * Wo >= 0.8 * regions * 128
-            hw_i, hw_o = Hi * Wi, Ho * Wo
-            if _WINO == "force" or (_WINO == "auto" and fit and 3 * Cin >= 32 and rows_ok(Cout) and
-                                    regions * _cdiv(Cout, 64) >= _WINO_MIN_WGS):
-                self.wino_fwd = self.wino3d = True
-                self.wino_fwd_geom = _wino_geom(
-                    [Cout, 3 * Cin, N * To, Hi, Wi, Ho, Wo, -1, -1, int(reflect), Cin * in_sc, in_sc, Wi, Cout * osp, osp, Wo,
-                     0, 4 * N * Cin * in_sc], To=To, in_st=hw_i, out_st=hw_o, cin=Cin, nkt=3, toff=-1, Ti=Ti,
-                    treflect=int(reflect))
-            Td, Hd, Wd = (Ti + 2, Hi + 2, Wi + 2) if reflect else (Ti, Hi, Wi)
-            dregions = N * Td * L.c2m_wino_regions(Hd, Wd)
-            dfit = N * Td * Hd * Wd >= _WINO_DFIT * dregions * 128
-            if _WINO == "force" or (_WINO == "auto" and dfit and 3 * Cout >= 32 and rows_ok(dM) and
-                                    dregions * _cdiv(dM, 64) >= _WINO_MIN_WGS):
-                self.wino_dgrad = self.wino3d = True
-                o = -2 if reflect else -1
-                # reflect in time: launched over the Ti real frames with the pad frames' contributions as extra (frame, tap)
-                # pairs of the frames they mirror onto (kernel: WinoP::ptab) -- not over Ti + 2 frames + a fold in time
-                self.wino3d_pairs = bool(reflect and Cout % 8 == 0 and To == Ti and Ti >= 2)
-                Tl = Ti if self.wino3d_pairs else Td
-                self.wino_dgrad_target = (N, Cin, Tl, Hd, Wd)
-                self.wino_dgrad_geom = _wino_geom(
-                    [dM, 3 * Cout, N * Tl, Ho, Wo, Hd, Wd, o, o, 0, Cout * osp, osp, Wo, Cin * Tl * Hd * Wd, Tl * Hd * Wd, Wd,
-                     0, 4 * N * Cout * osp], To=Tl, in_st=hw_o, out_st=Hd * Wd, cin=Cout, nkt=3, toff=o, Ti=To, treflect=0)
-                if self.wino3d_pairs:
-                    self.wino_pair_tab = torch.from_numpy(_time_pair_table(Ti).reshape(-1)).to(device)
-                    self.wino_dgrad_geom[WG.PTAB] = self.wino_pair_tab.data_ptr()
-                    # every launched frame is a real one: the two-target epilogue of the 2-D layers applies per frame (interior
-                    # straight into dX, only the pad ring into the scratch tensor; then the border-only fold)
-                    self.wino_dgrad_geom[WG.Y2_SN:WG.EXT_X + 1] = (Cin * in_sc, in_sc, Wi, 1, 1, Hi, Wi)
-            # weight gradient: the 2-D Winograd wgrad kernel over images (sample, frame) and virtual channels (kt, ci)
-            self.wino_wgrad = self.wino_wgrad3d = wino_wgrad_pays(3 * Cin, N * Ti)
-        # ---- forward
-        self.ck = ck = _choose_ck(Cin, taps)
-        self.fwd_patch = False
-        # channel-blocked input (conv_nc8.hip): 2-D bf16 patch layers whose planes are whole 8-pixel groups
-        self.nc8 = bool(bf16 and _NC8 and nd == 2 and (Hi * Wi) % 8 == 0 and (Ho * Wo) % 8 == 0)
+        if ly.bf16 or ly.nd != 3 or not ly.is_333_s1p1:
+            return
+        if _wino_gate(N * To * L.c2m_wino_regions(Ho, Wo), N * To * Ho * Wo, 0.8, 3 * Cin, Cout):
+            self.wino_fwd = self.wino3d = True
+            self.wino_fwd_geom = _wino_geom(m=Cout, k=3 * Cin, nimg=N * To, hi=Hi, wi=Wi, ho=Ho, wo=Wo, iy0=-1, ix0=-1, reflect=int(reflect),
+                                            in_sn=Cin * in_sc, in_sc=in_sc, in_sh=Wi, out_sn=Cout * osp, out_sc=osp, out_sh=Wo,
+                                            x_bytes=4 * N * Cin * in_sc, to=To, in_st=Hi * Wi, out_st=Ho * Wo, cin=Cin, nkt=3, toff=-1,
+                                            ti=Ti, treflect=int(reflect))
+        Td, Hd, Wd = (Ti + 2, Hi + 2, Wi + 2) if reflect else (Ti, Hi, Wi)
+        if _wino_gate(N * Td * L.c2m_wino_regions(Hd, Wd), N * Td * Hd * Wd, _WINO_DFIT, 3 * Cout, ly.dM):
+            self.wino_dgrad = self.wino3d = True
+            o = -2 if reflect else -1
+            # reflect in time: launched over the Ti real frames with the pad frames' contributions as extra (frame, tap)
+            # pairs of the frames they mirror onto (kernel: WinoP::ptab) -- not over Ti + 2 frames + a fold in time
+            self.wino3d_pairs = bool(reflect and Cout % 8 == 0 and To == Ti and Ti >= 2)
+            Tl = Ti if self.wino3d_pairs else Td
+            self.wino_dgrad_target = (N, Cin, Tl, Hd, Wd)
+            pairs = {}
+            if self.wino3d_pairs:
+                self.wino_pair_tab = torch.from_numpy(_time_pair_table(Ti).reshape(-1)).to(device)
+                # every launched frame is a real one: the two-target epilogue of the 2-D layers applies per frame (interior
+                # straight into dX, only the pad ring into the scratch tensor; then the border-only fold)
+                pairs = dict(_wino_interior(ly), ptab=self.wino_pair_tab.data_ptr())
+            self.wino_dgrad_geom = _wino_geom(m=ly.dM, k=3 * Cout, nimg=N * Tl, hi=Ho, wi=Wo, ho=Hd, wo=Wd, iy0=o, ix0=o,
+                                              in_sn=Cout * osp, in_sc=osp, in_sh=Wo, out_sn=Cin * Tl * Hd * Wd, out_sc=Tl * Hd * Wd, out_sh=Wd,
+                                              x_bytes=4 * N * Cout * osp, to=Tl, in_st=Ho * Wo, out_st=Hd * Wd, cin=Cout, nkt=3, toff=o,
+                                              ti=To, **pairs)
+        # weight gradient: the 2-D Winograd wgrad kernel over images (sample, frame) and virtual channels (kt, ci)
+        self.wino_wgrad = self.wino_wgrad3d = self._wino_wgrad_pays(ly, L, 3 * Cin, N * Ti)
+
+    def _plan_nc8(self, ly, device):
+        """Which NC8 patch kernels (conv_nc8.hip, bf16 mode) can take the layer.
+        Sets: nc8, k333_nc8, k333_wgrad_nc8, k333_dgrad_nc8, s2_nc8, s2_dgrad_nc8, s2_wgrad_nc8, wgrad_nc8 (always); k333_ptab
+        where k333_dgrad_nc8.  Reads: the layer only."""
+        N, Cin, Cout, Hi, Wi, Ho, Wo, reflect, dM = ly.N, ly.Cin, ly.Cout, ly.Hi, ly.Wi, ly.Ho, ly.Wo, ly.reflect, ly.dM
+        # channel-blocked input: 2-D bf16 patch layers whose planes are whole 8-pixel groups
+        self.nc8 = bool(ly.bf16 and _NC8 and ly.nd == 2 and (Hi * Wi) % 8 == 0 and (Ho * Wo) % 8 == 0)
         # ... the 3x3x3 stride-1 pad-1 layers as (sample, frame) images with (time tap, channel) chunks: forward and weight gradient
         # (channel padding up to 45 %: final_fuse has 34 input channels = three 16-channel chunks, still 2x the gather kernel)
-        k333 = bool(bf16 and _NC8 and nd == 3 and (kt, kh, kw) == (3, 3, 3) and tuple(stride) == (1, 1, 1) and
-                    (pt, ph, pw) == (1, 1, 1) and (Hi * Wi) % 8 == 0 and Ti >= 2 and Cin >= 12 and _ceil(Cin, 16) <= 1.45 * Cin and
-                    Wo >= 32 and Ho >= 8 and (_ceil(Wo, 32) * _ceil(Ho, 8)) <= _NC8_FILL * Wo * Ho)
+        k333 = bool(ly.bf16 and _NC8 and ly.nd == 3 and ly.is_333_s1p1 and (Hi * Wi) % 8 == 0 and ly.Ti >= 2 and _chan16_ok(Cin, 1.45) and
+                    Wo >= 32 and Ho >= 8 and _fill_ok(Ho, Wo, _NC8_FILL))
         self.k333_nc8 = k333 and Cout > 4
         self.k333_wgrad_nc8 = k333 and Cout >= 64 and Cin >= 16
         pd = 1 if reflect else 0
-        self.k333_dgrad_nc8 = bool(k333 and Cout >= 12 and _ceil(Cout, 16) <= 1.25 * Cout and dM > 4 and
-                                   (_ceil(Wi + 2 * pd, 32) * _ceil(Hi + 2 * pd, 8)) <= _NC8_FILL * (Wi + 2 * pd) * (Hi + 2 * pd))
+        self.k333_dgrad_nc8 = bool(k333 and _chan16_ok(Cout, 1.25) and dM > 4 and _fill_ok(Hi + 2 * pd, Wi + 2 * pd, _NC8_FILL))
         if self.k333_dgrad_nc8:
-            self.k333_ptab = torch.from_numpy(_time_pair_table_kt(Ti, bool(reflect)).reshape(-1)).to(device)
+            self.k333_ptab = torch.from_numpy(_time_pair_table_kt(ly.Ti, bool(reflect)).reshape(-1)).to(device)
         # ... the 4x4 stride-2 pad-1 layers on the parity-plane form of the patch kernel (forward).  Half-filled tiles (8 x 16 output maps)
         # go to the NC8 gather form where it can take the layer: 40 vs 59 us on 256 -> 512 at 16x32, but 42 vs 36 us on 128 -> 256 at
         # 32x64 whose tiles are full (profiles/r04_ab_nc8.txt)
         # (only launches with >= 4096 output pixels: below that the gather form needs deep K splits -- configs[2]'s 20-image batches of
         # the same layers measured +0.7 ms with the gather form, configs[3]'s 40-image batches -0.7 ms)
-        g8_in = bool(_G8 and Cin >= 12 and _ceil(Cin, 16) <= 1.45 * Cin and in_sc % 8 == 0 and N * osp >= 4096)
-        g8_out = bool(_G8 and Cout >= 12 and _ceil(Cout, 16) <= 1.45 * Cout and osp % 8 == 0 and N * osp >= 4096)
-        self.s2_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and (ph, pw) == (1, 1)
-                           and Hi % 2 == 0 and Wi % 2 == 0 and Cout > 4 and Cin >= 12 and Wo >= 16 and Ho >= 4 and
-                           (_ceil(Wo, 32) * _ceil(Ho, 8)) <= (_NC8_S2_FILL_G8 if g8_in else _NC8_FILL) * Wo * Ho)
+        g8_in = bool(_G8 and _chan16_ok(Cin, 1.45) and ly.in_sc % 8 == 0 and N * ly.osp >= 4096)
+        g8_out = bool(_G8 and _chan16_ok(Cout, 1.45) and ly.osp % 8 == 0 and N * ly.osp >= 4096)
+        s2 = self.nc8 and ly.is_4x4_s2p1_even
+        self.s2_nc8 = bool(s2 and Cout > 4 and Cin >= 12 and Wo >= 16 and Ho >= 4 and
+                           _fill_ok(Ho, Wo, _NC8_S2_FILL_G8 if g8_in else _NC8_FILL))
         # ... their data gradient (four output parity classes over one shared dY patch, one launch)
-        qh, qw = Hi // 2 + (1 if reflect else 0), Wi // 2 + (1 if reflect else 0)
-        self.s2_dgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
-                                 (ph, pw) == (1, 1) and Hi % 2 == 0 and Wi % 2 == 0 and Cin >= 8 and Cout >= 12 and qw >= 16 and
-                                 dM == Cin and (_ceil(qw, 32) * _ceil(qh, 8)) <= (_NC8_S2_FILL_G8 if (g8_out and dM > 4) else _NC8_FILL) * qw * qh)
-        self.s2_wgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 4, 4) and tuple(stride) == (1, 2, 2) and
-                                 (ph, pw) == (1, 1) and Hi % 2 == 0 and Wi % 2 == 0 and Cout >= 64 and Cin >= 16 and
+        qh, qw = Hi // 2 + pd, Wi // 2 + pd
+        self.s2_dgrad_nc8 = bool(s2 and Cin >= 8 and Cout >= 12 and qw >= 16 and dM == Cin and
+                                 _fill_ok(qh, qw, _NC8_S2_FILL_G8 if (g8_out and dM > 4) else _NC8_FILL))
+        self.s2_wgrad_nc8 = bool(s2 and Cout >= 64 and Cin >= 16 and
                                  N * Ho * Wo >= _NC8_S2_WGRAD_MIN_PIX)      # (the few-pixel encoder tails: one or two chunks per split, slabs dominate)
         # ... and the weight gradient of the 3x3 stride-1 pad-1 layers from the NC8 forms of X and dY (transposed LDS reads)
-        self.wgrad_nc8 = bool(self.nc8 and (kt, kh, kw) == (1, 3, 3) and tuple(stride) == (1, 1, 1) and
-                              (ph, pw) == (1, 1) and Cout >= 64 and Cin >= 16)      # (Cout = 32: half of a 64-row tile is padding -- 88 vs 145 TF/s on the NCHW kernel)
-        if (kt, kh, kw) == (1, 3, 3) and (_patch_bf16_ok(Cin, stride, Ho, Wo, Cout, None, self.nc8) if bf16 else
-                                          _patch_ok(Cin, (kt, kh, kw), stride, 1, Ho, Wo, Cout)):
-            self.fwd_patch, self.ck = True, 16
-            ck = 16
-        ns = 16 // ck
-        offs = _tap_offsets(kt, kh, kw, np.arange(kt) - pt, np.arange(kh) - ph, np.arange(kw) - pw)
+        self.wgrad_nc8 = bool(self.nc8 and ly.is_3x3_s1p1 and Cout >= 64 and Cin >= 16)      # (Cout = 32: half of a 64-row tile is padding -- 88 vs 145 TF/s on the NCHW kernel)
+
+    def _plan_forward(self, ly, L, device):
+        """The direct (implicit-GEMM / LDS-patch) forward launch; returns the tap offsets for the stages that share them.
+        Sets: ck, fwd_patch, nk, fwd_tab, fwd_splits, fwd_geom.  Reads: nc8."""
+        N, Cin, Cout, Ho, Wo, kt, kh, kw, in_sc, osp = ly.N, ly.Cin, ly.Cout, ly.Ho, ly.Wo, ly.kt, ly.kh, ly.kw, ly.in_sc, ly.osp
+        self.fwd_patch = ly.k == (1, 3, 3) and (_patch_bf16_ok(Cin, ly.stride, Ho, Wo, Cout, None, self.nc8) if ly.bf16 else
+                                                _patch_ok(Cin, ly.k, ly.stride, 1, Ho, Wo, Cout))
+        self.ck = ck = 16 if self.fwd_patch else _choose_ck(Cin, ly.taps)
+        offs = _tap_offsets(kt, kh, kw, np.arange(kt) - ly.pt, np.arange(kh) - ly.ph, np.arange(kw) - ly.pw)
         tab, nch, ntg = _kstep_table(Cin, offs, in_sc, ck)
-        nk = nch * ntg
-        self.nk = nk
+        self.nk = nk = nch * ntg
         self.fwd_tab = torch.from_numpy(tab.reshape(-1)).to(device)
-        self.fwd_splits = _patch_splits(L, Cout, Cin, N * osp, bf16) if self.fwd_patch else \
-            _splits(L, Cout, nk, N * osp, bf16)
-        self.fwd_geom = _geom(M=Cout, nk=nk, lda=nk * 16, Npix=N * osp, To=To, Ho=Ho, Wo=Wo, Ti=Ti, Hi=Hi, Wi=Wi, st=st,
-                              sh=sh, sw=sw, in_sn=Cin * in_sc, in_st=Hi * Wi, in_sh=Wi, out_sn=Cout * osp, out_sc=osp,
-                              out_st=Ho * Wo, out_sh=Wo, out_sw=1, out_off=0, reflect=int(reflect), is3d=is3d, ns=ns,
-                              in_sc=in_sc, splits=self.fwd_splits, slab_stride=N * Cout * osp,
-                              x_bytes=4 * N * Cin * in_sc)
-        self.fwd_geom[[G.CIN, G.TAPS, G.NTG, G.PRECISION]] = (Cin, taps, ntg, int(bf16))      # (precision: read by c2m_conv_igemm / c2m_conv_wgrad)
-        if kt == 1 and kh == kw and (st, sh, sw) == (1, 1, 1):
-            self.fwd_geom[G.SQUARE_KW] = kw                # row-major square tap set, dx ascending (thin row-blocked kernel)
+        self.fwd_splits = _patch_splits(L, Cout, Cin, N * osp, ly.bf16) if self.fwd_patch else \
+            _splits(L, Cout, nk, N * osp, ly.bf16)
+        self.fwd_geom = _geom(M=Cout, nk=nk, lda=nk * 16, Npix=N * osp, To=ly.To, Ho=Ho, Wo=Wo, Ti=ly.Ti, Hi=ly.Hi, Wi=ly.Wi, st=ly.st,
+                              sh=ly.sh, sw=ly.sw, in_sn=Cin * in_sc, in_st=ly.Hi * ly.Wi, in_sh=ly.Wi, out_sn=Cout * osp, out_sc=osp,
+                              out_st=Ho * Wo, out_sh=Wo, out_sw=1, out_off=0, reflect=int(ly.reflect), is3d=self.is3d, ns=16 // ck,
+                              in_sc=in_sc, splits=self.fwd_splits, slab_stride=N * Cout * osp, x_bytes=4 * N * Cin * in_sc,
+                              Cin=Cin, taps=ly.taps, ntg=ntg, precision=int(ly.bf16))      # (precision: read by c2m_conv_igemm / c2m_conv_wgrad)
+        if kt == 1 and kh == kw and ly.stride == (1, 1, 1):
+            self.fwd_geom[G.SQUARE_KW] = kw              # row-major square tap set, dx ascending (thin row-blocked kernel)
         if self.fwd_patch:
-            _set_patch(self.fwd_geom, -ph, -pw, (0, 1, 2), (0, 1, 2))
-            if bf16:
+            _set_patch(self.fwd_geom, -ly.ph, -ly.pw, (0, 1, 2), (0, 1, 2))
+            if ly.bf16:
                 self.fwd_geom[G.LDA] = _ceil(Cout, 128)       # lda = padded row count of the bf16 weight image
-        # ---- wgrad: same (chunk, tap group) row order + a ones group (bias gradient) + zero groups up to the tile
+        return offs
+
+    def _plan_wgrad(self, ly, L, offs, device):
+        """The direct weight gradient: the forward's (chunk, tap group) row order + a ones group (bias gradient) + zero groups up to
+        the tile.  Sets: J, wg_tab, wg_geom, wg_splits.  Reads: ck, nk, fwd_geom."""
+        N, Cout, Wi, Wo, kw, osp, nk = ly.N, ly.Cout, ly.Wi, ly.Wo, ly.kw, ly.osp, self.nk
         self.J = L.c2m_conv_wgrad_rows(Cout, nk + 1)
-        wtab, _, _ = _kstep_table(Cin, offs, in_sc, ck, extra_groups=self.J // 16 - nk - 1, ones_group=True)
+        wtab, _, _ = _kstep_table(ly.Cin, offs, ly.in_sc, self.ck, extra_groups=self.J // 16 - nk - 1, ones_group=True)
         self.wg_tab = torch.from_numpy(wtab.reshape(-1)).to(device)
-        self.wg_geom = self.fwd_geom.copy()
-        self.wg_geom[G.PATCH] = 0
-        self.wg_geom[[G.M, G.NK, G.OUT_SN, G.OUT_SC]] = (Cout, self.J, Cout * osp, osp)      # (wgrad: J rows, dY strides)
-        self.wg_geom[[G.CIN, G.TAPS, G.NTG, G.NGROUPS]] = (Cin, taps, ntg, nk)
-        self.wg_geom[G.DY_BYTES] = 4 * N * Cout * osp
+        self.wg_geom = self.fwd_geom.copy()      # (M rows of dY with the output's strides; Cin, taps, tap groups: the forward's)
+        self.wg_geom[[G.PATCH, G.NK, G.NGROUPS, G.DY_BYTES]] = (0, self.J, nk, 4 * N * Cout * osp)      # (wgrad: J rows, nk of them K-step groups)
         # bf16 data path: the 16-byte-load weight-gradient kernel (conv_wgrad_wide_bf16_kernel) takes layers whose 8-pixel
         # groups stay inside an input row up to one pad pixel: unit x stride, same-width output, |tap dx| <= 1
-        self.wg_geom[G.WGRAD_WIDE] = int(bf16 and sw == 1 and Wi == Wo and Wo % 8 == 0 and Wi >= 8 and kw in (1, 3)
-                               and pw == (kw - 1) // 2 and osp % 8 == 0)
+        self.wg_geom[G.WGRAD_WIDE] = int(ly.bf16 and ly.sw == 1 and Wi == Wo and Wo % 8 == 0 and Wi >= 8 and kw in (1, 3)
+                                         and ly.pw == (kw - 1) // 2 and osp % 8 == 0)
         # ... and its stride-2 form (4-wide taps, pad 1: dx = -1 .. 2; every second element of a 16-element run)
-        if bf16 and sw == 2 and Wi == 2 * Wo and Wo % 8 == 0 and kw == 4 and pw == 1 and osp % 8 == 0:
+        if ly.bf16 and ly.sw == 2 and Wi == 2 * Wo and Wo % 8 == 0 and kw == 4 and ly.pw == 1 and osp % 8 == 0:
             self.wg_geom[G.WGRAD_WIDE] = 2
         self.wg_splits = L.c2m_conv_wgrad_splits(Cout, self.J, N * osp)
-        # ---- dgrad: one launch per stride-parity class
+
+    def _plan_dgrad_classes(self, ly, L, device):
+        """The direct data gradient: one launch per stride-parity class, with the split count the classes share.
+        Sets: dgrad_target, dgrad_needs_zero, classes (dicts: r, taps, ck, nk, npix, patch, tab, geom, offs), dgrad_splits,
+        fwd_flops, dgrad_flops, dgrad_work.  Reads: K."""
+        N, Cin, Cout, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, pt, ph, pw, _, reflect, bf16, dM, in_sc, osp, _ = ly
         Tp, Hp, Wp = (Ti + 2 * pt, Hi + 2 * ph, Wi + 2 * pw) if reflect else (Ti, Hi, Wi)
         self.dgrad_target = (N, Cin, Tp, Hp, Wp)
         self.dgrad_needs_zero = False
@@ -1062,13 +1130,11 @@ class _ConvPlan:
             for (ry, Ay, qy, Qy, offy) in dim_classes(Hi, Ho, kh, sh, ph):
                 for (rx, Ax, qx, Qx, offx) in dim_classes(Wi, Wo, kw, sw, pw):
                     ctaps = At * Ay * Ax
-                    cck = _choose_ck(Cout, ctaps)
-                    cpatch = False
-                    if (At, Ay, Ax) == (1, 3, 3) and (st, sh, sw) == (1, 1, 1) and \
-                            (_patch_bf16_ok(Cout, (1, 1, 1), Qy, Qx, dM, _NC8_DGRAD_FILL if (reflect and _G8) else None,
-                                            not is3d and (Ho * Wo) % 8 == 0) if bf16 else
-                             _patch_ok(Cout, (At, Ay, Ax), (1, 1, 1), 1, Qy, Qx, dM)):
-                        cpatch, cck = True, 16
+                    cpatch = (At, Ay, Ax) == (1, 3, 3) and (st, sh, sw) == (1, 1, 1) and \
+                        (_patch_bf16_ok(Cout, (1, 1, 1), Qy, Qx, dM, _NC8_DGRAD_FILL if (reflect and _G8) else None,
+                                        not self.is3d and (Ho * Wo) % 8 == 0) if bf16 else
+                         _patch_ok(Cout, (At, Ay, Ax), (1, 1, 1), 1, Qy, Qx, dM))
+                    cck = 16 if cpatch else _choose_ck(Cout, ctaps)
                     coffs = _tap_offsets(At, Ay, Ax, qt - np.arange(At), qy - np.arange(Ay), qx - np.arange(Ax))
                     ctab, cnch, cntg = _kstep_table(Cout, coffs, osp, cck)
                     cnk = cnch * cntg
@@ -1076,11 +1142,11 @@ class _ConvPlan:
                     geom = _geom(M=dM, nk=cnk, lda=cnk * 16, Npix=npix, To=Qt, Ho=Qy, Wo=Qx, Ti=To, Hi=Ho, Wi=Wo, st=1,
                                  sh=1, sw=1, in_sn=Cout * osp, in_st=Ho * Wo, in_sh=Wo, out_sn=Cin * Tp * Hp * Wp,
                                  out_sc=Tp * Hp * Wp, out_st=st * Hp * Wp, out_sh=sh * Wp, out_sw=sw,
-                                 out_off=offt * Hp * Wp + offy * Wp + offx, reflect=0, is3d=is3d, ns=16 // cck,
-                                 in_sc=osp, splits=1, slab_stride=tgt_numel, x_bytes=4 * N * Cout * osp)
+                                 out_off=offt * Hp * Wp + offy * Wp + offx, reflect=0, is3d=self.is3d, ns=16 // cck,
+                                 in_sc=osp, splits=1, slab_stride=tgt_numel, x_bytes=4 * N * Cout * osp,
+                                 Cin=Cout, taps=ctaps, ntg=cntg, precision=int(bf16))
                     # two-target epilogue (reflect): padded coord = q*stride + r per dim; interior = [pad, pad + extent)
                     geom[G.PS_T:G.Y2_SH + 1] = (st, sh, sw, offt, offy, offx, pt, ph, pw, Ti, Hi, Wi, Cin * in_sc, in_sc, Hi * Wi, Wi)
-                    geom[[G.CIN, G.TAPS, G.NTG, G.PRECISION]] = (Cout, ctaps, cntg, int(bf16))
                     if At == 1 and Ay == Ax and (st, sh, sw) == (1, 1, 1):
                         geom[G.SQUARE_KW] = -Ax            # data gradient: tap offsets run q - arange(A): dx descending
                     if cpatch:
@@ -1091,11 +1157,8 @@ class _ConvPlan:
                                              tab=torch.from_numpy(ctab.reshape(-1)).to(device), geom=geom, offs=coffs))
         # common split count for all classes (they share one slab set); fall back to 1 if they cannot agree
         S = min(_splits(L, dM, c["nk"], c["npix"], bf16) for c in self.classes) if self.classes else 1
-        if S > 1:
-            for c in self.classes:
-                if _cdiv(c["nk"], _cdiv(c["nk"], S)) != S:
-                    S = 1
-                    break
+        if S > 1 and any(_cdiv(c["nk"], _cdiv(c["nk"], S)) != S for c in self.classes):
+            S = 1
         if any(c["patch"] for c in self.classes):        # stride-1 3x3: a single class
             S = _patch_splits(L, dM, Cout, self.classes[0]["npix"], bf16)
         self.dgrad_splits = S
@@ -1107,17 +1170,21 @@ class _ConvPlan:
         self.fwd_flops = 2.0 * Cout * self.K * N * osp
         self.dgrad_flops = self.fwd_flops * dM / Cin
         self.dgrad_work = float(sum(c["taps"] * c["npix"] for c in self.classes)) or 1.0
-        # ---- class batching: the stride parity classes of a k % s == 0 conv share every dimension (same taps per
-        # class, same Q extents) and differ only in weights, tap table and output origin -> ONE launch
-        # (blockIdx.z = class), which fills the chip where a single class (1/s^d of the pixels) cannot
+
+    def _plan_class_batching(self, ly, L):
+        """Class batching: the stride parity classes of a k % s == 0 conv share every dimension (same taps per class, same Q extents)
+        and differ only in weights, tap table and output origin -> ONE launch (blockIdx.z = class), which fills the chip where a
+        single class (1/s^d of the pixels) cannot.
+        Sets: classes_packable, cls_batch (None, or a dict: groups (dicts: geom, tab, ncls, first, npix), ncls, ck, taps, nk); with
+        cls_batch, dgrad_splits again.  Reads: classes, dgrad_needs_zero."""
+        Cin, st, sh, sw = ly.Cin, ly.st, ly.sh, ly.sw
         self.cls_batch = None
         cl = self.classes
         ncls = st * sh * sw
-        self.classes_packable = len(cl) == ncls and kt % st == 0 and kh % sh == 0 and kw % sw == 0 and \
-            len({(c["ck"], c["taps"]) for c in cl}) == 1 and \
+        whole = len(cl) == ncls and ly.kt % st == 0 and ly.kh % sh == 0 and ly.kw % sw == 0      # every parity class, each with k / s taps per dim
+        self.classes_packable = whole and len({(c["ck"], c["taps"]) for c in cl}) == 1 and \
             [c["r"] for c in cl] == [(a, b, c_) for a in range(st) for b in range(sh) for c_ in range(sw)]
-        if 1 < ncls <= 8 and len(cl) == ncls and kt % st == 0 and kh % sh == 0 and kw % sw == 0 and \
-                not self.dgrad_needs_zero and not any(c["patch"] for c in cl) and \
+        if 1 < ncls <= 8 and whole and not self.dgrad_needs_zero and not any(c["patch"] for c in cl) and \
                 len({(c["nk"], c["ck"], c["taps"]) for c in cl}) == 1:
             key = lambda c: (c["npix"],) + tuple(int(v) for v in c["geom"][G.TO:G.WO + 1])
             runs, i = [], 0
@@ -1128,7 +1195,7 @@ class _ConvPlan:
                 runs.append((i, j + 1))
                 i = j + 1
             nk0, ck0 = cl[0]["nk"], cl[0]["ck"]
-            SB = min(_splits(L, Cin, nk0, cl[a]["npix"] * (b - a), bf16) for a, b in runs)
+            SB = min(_splits(L, Cin, nk0, cl[a]["npix"] * (b - a), ly.bf16) for a, b in runs)
             groups = []
             for a, b in runs:
                 g = cl[a]["geom"].copy()
@@ -1144,32 +1211,31 @@ class _ConvPlan:
             if len(groups) < ncls:
                 self.cls_batch = dict(groups=groups, ncls=ncls, ck=ck0, taps=cl[0]["taps"], nk=nk0)
                 self.dgrad_splits = SB
-        # ---- NC8 gather form (conv_gather_nc8_kernel) of every bf16 forward / data gradient the NC8 patch forms above do not take:
-        # the same launches (geometry, classes, two-target epilogue, split-K) with channel-blocked input, a compact tap table and
-        # bf16 weights in (tap, chunk) order.  Channel padding up to 45 % (34 -> 48); <= 4 output rows stay on the vector-ALU kernels.
-        chan_ok = lambda c: c >= 12 and _ceil(c, 16) <= 1.45 * c
-        g8 = bool(bf16 and _NC8 and _G8)
-        self.g8_fwd = bool(g8 and not (self.k333_nc8 or self.s2_nc8 or (self.fwd_patch and self.nc8)) and Cout > 4 and chan_ok(Cin)
-                           and in_sc % 8 == 0 and taps <= 64)
+
+    def _plan_g8(self, ly, offs, device):
+        """NC8 gather form (conv_gather_nc8_kernel) of every bf16 forward / data gradient the NC8 patch forms do not take: the same
+        launches (geometry, classes, two-target epilogue, split-K) with channel-blocked input, a compact tap table and bf16 weights in
+        (tap, chunk) order.  Channel padding up to 45 % (34 -> 48); <= 4 output rows stay on the vector-ALU kernels.
+        Sets: g8_fwd, g8_dgrad (always); g8_fwd_splits, g8_fwd_geom, g8_fwd_tab where g8_fwd; g8_a_cls, g8_dgrad_splits and, on every
+        class and batch group, "g8" and "g8tab" where g8_dgrad.  Reads: the NC8 flags, fwd_patch, fwd_geom, classes, classes_packable,
+        cls_batch; offs: the forward's tap offsets."""
+        N, Cin, Cout, dM, osp, taps, cl = ly.N, ly.Cin, ly.Cout, ly.dM, ly.osp, ly.taps, self.classes
+        g8 = bool(ly.bf16 and _NC8 and _G8)
+        self.g8_fwd = bool(g8 and not (self.k333_nc8 or self.s2_nc8 or self._fwd_on_patch_nc8()) and Cout > 4 and _chan16_ok(Cin, 1.45)
+                           and ly.in_sc % 8 == 0 and taps <= 64)
         if self.g8_fwd:
             self.g8_fwd_splits = _g8_splits(Cout, taps * _cdiv(Cin, 16), N * osp)
             self.g8_fwd_geom = _g8_geom(self.fwd_geom, Cin, taps, self.g8_fwd_splits)
             self.g8_fwd_tab = _g8_taps(offs, device)
-        # data gradient on the NC8 patch kernel: the single 3x3 stride-1 class of a bf16 layer whose dY planes are whole 8-pixel groups.
-        # (the ONE spelling; the three it replaces differed only in whether they tested bf16 / _NC8 themselves or sat behind a test of
-        # them -- `g8`, below, holds both, and patch classes are one class, so any() == all())
-        patch_nc8 = bool(bf16 and _NC8 and cl and all(c["patch"] for c in cl) and not is3d and (Ho * Wo) % 8 == 0)
-        self.g8_dgrad = bool(g8 and cl and not (self.k333_dgrad_nc8 or self.s2_dgrad_nc8 or patch_nc8) and dM > 4 and chan_ok(Cout)
-                             and osp % 8 == 0 and self.classes_packable and max(c["taps"] for c in cl) <= 64 and
-                             not any(c["patch"] for c in cl))
+        self.g8_dgrad = bool(g8 and cl and not (self.k333_dgrad_nc8 or self.s2_dgrad_nc8 or self._dgrad_on_patch_nc8()) and dM > 4
+                             and _chan16_ok(Cout, 1.45) and osp % 8 == 0 and self.classes_packable and max(c["taps"] for c in cl) <= 64 and
+                             not any(c["patch"] for c in cl))      # (a patch class off the 8-pixel grid: the NCHW patch kernel)
         if self.g8_dgrad:
             ctaps = cl[0]["taps"]
             nk8 = ctaps * _cdiv(Cout, 16)
             self.g8_a_cls = nk8 * 2 * _ceil(dM, 128) * 16          # bytes of one class image
-            if self.cls_batch is not None:
-                S8 = min(_g8_splits(dM, nk8, grp["npix"], grp["ncls"]) for grp in self.cls_batch["groups"])
-            else:
-                S8 = min(_g8_splits(dM, nk8, c["npix"]) for c in cl)
+            S8 = min(_g8_splits(dM, nk8, grp["npix"], grp["ncls"]) for grp in self.cls_batch["groups"]) if self.cls_batch is not None else \
+                min(_g8_splits(dM, nk8, c["npix"]) for c in cl)
             if S8 > 1 and _cdiv(nk8, _cdiv(nk8, S8)) != S8:
                 S8 = 1
             self.g8_dgrad_splits = S8
@@ -1180,39 +1246,45 @@ class _ConvPlan:
                 grp["g8"] = _g8_geom(grp["geom"], Cout, ctaps, S8)
                 grp["g8"][G.A_CLS], grp["g8"][G.KTAB_CLS] = 0, 0
                 grp["g8tab"] = torch.cat([c["g8tab"] for c in cl[grp["first"]:grp["first"] + grp["ncls"]]])
-        # ---- routes: the kernel each pass of this layer runs on, by name (_ROUTE_PROF lists them).  The eligibility flags are read HERE
-        # only, in order of precedence (the NC8 flags hold `bf16` themselves, the Winograd ones `not bf16`); dispatch, the NC8-only
-        # predicates and the NC8 keep decisions read the names.  Knobs (_NC8, _G8, _WINO, ...) are fixed when the plan is built.
+
+    def _plan_routes(self):
+        """The kernel each pass of this layer runs on, by name (_ROUTE_PROF lists them).  The eligibility flags are read HERE only, in
+        order of precedence (the NC8 flags hold `bf16` themselves, the Winograd ones `not bf16`); dispatch, the NC8-only predicates
+        and the NC8 keep decisions read the names.  Knobs (_NC8, _G8, _WINO, ...) are fixed when the plan is built.
+        Sets: fwd_route, dgrad_route, wgrad_route, keep_x_nc8, keep_dy_nc8.  Reads: every eligibility flag, cls_batch, classes."""
         self.fwd_route = (("wino3d" if self.wino3d else "wino4" if self.wino4_fwd else "wino") if self.wino_fwd else
                           "k333_nc8" if self.k333_nc8 else "s2_nc8" if self.s2_nc8 else "g8" if self.g8_fwd else
-                          "patch_nc8" if (self.fwd_patch and self.nc8) else "igemm")
+                          "patch_nc8" if self._fwd_on_patch_nc8() else "igemm")
         self.dgrad_route = (("wino3d" if self.wino3d else ("wino4" if self.wino4_dgrad else "wino") + ("_ring" if self.ring_dgrad else ""))
                             if self.wino_dgrad else
                             "k333_nc8" if self.k333_dgrad_nc8 else "s2_nc8" if self.s2_dgrad_nc8 else "g8" if self.g8_dgrad else
-                            "igemm_batched" if self.cls_batch is not None else "patch_nc8" if patch_nc8 else "igemm")
+                            "igemm_batched" if self.cls_batch is not None else "patch_nc8" if self._dgrad_on_patch_nc8() else "igemm")
         self.wgrad_route = ("k333_nc8" if self.k333_wgrad_nc8 else "nc8" if self.wgrad_nc8 else "s2_nc8" if self.s2_wgrad_nc8 else
                             "wino3d" if self.wino_wgrad3d else "wino" if self.wino_wgrad else "igemm")
         # X in NC8 form goes from the forward launch to the weight gradient (ctx.nc8_keep); dY in NC8 form is shared by the two gradients
-        # of a backward node (`keep`).  keep_dy_nc8 is NOT the flag expression it replaces (bf16 and (nc8 or k333 wgrad / dgrad)): it
-        # also pins dY for g8 data gradients of 3-D layers and no longer makes an unused dict for 2-D layers without an NC8 route --
-        # the same layout passes either way (_to_nc8 also remembers its result on the tensor)
+        # of a backward node (`keep`)
         self.keep_x_nc8 = self.fwd_route in _NC8_KEEPS_X and self.wgrad_route in _NC8_WGRADS
         self.keep_dy_nc8 = self.dgrad_route in _NC8_CONVS or self.wgrad_route in _NC8_WGRADS
-        # ---- what is the same for every call.  bf16 data path: bf16 in, bf16 out, except the <= 4-channel heads (flow, occlusion, RGB):
-        # fp32 out, and fp32 in on the vector-ALU kernels when the launch is big enough for them (_thin)
+
+    def _plan_call_constants(self, ly):
+        """What is the same for every call.  bf16 data path: bf16 in, bf16 out, except the <= 4-channel heads (flow, occlusion, RGB):
+        fp32 out, and fp32 in on the vector-ALU kernels when the launch is big enough for them (_thin).
+        Sets: fwd_xdt, fwd_ydt, in_shape, dgrad_route_splits, dgrad_folded, dgrad_two_target, "thin" on every class, fwd_prof,
+        dgrad_prof, wgrad_prof.  Reads: the routes, fwd_splits, g8_fwd_splits, dgrad_splits, g8_dgrad_splits, wg_splits,
+        dgrad_needs_zero, cls_batch, classes, dims, stride, pad, K."""
+        N, Cin, Cout, bf16, osp = ly.N, ly.Cin, ly.Cout, ly.bf16, ly.osp
         thin = bool(bf16 and _thin(Cout, self.fwd_splits, N * osp))
         self.fwd_xdt = BF16 if (bf16 and not thin) else torch.float32
         self.fwd_ydt = BF16 if (bf16 and not thin and Cout > 4) else torch.float32
-        self.in_shape = (N, Cin, Ti, Hi, Wi) if nd == 3 else (N, Cin, Hi, Wi)
+        self.in_shape = (N, Cin, ly.Ti, ly.Hi, ly.Wi) if ly.nd == 3 else (N, Cin, ly.Hi, ly.Wi)
         S = self.dgrad_route_splits = self.g8_dgrad_splits if self.dgrad_route == "g8" else self.dgrad_splits
-        self.dgrad_folded = bool(reflect and any(pad))
+        self.dgrad_folded = bool(ly.reflect and any(self.pad))
         self.dgrad_two_target = self.dgrad_folded and S == 1 and not self.dgrad_needs_zero
-        for c in cl:        # (a <= 4-channel input: such launches are fp32 in, fp32 out, and then the layer's target is fp32)
-            c["thin"] = bool(bf16 and self.cls_batch is None and _thin(dM, S, c["npix"], self.dgrad_two_target))
-
+        for c in self.classes:        # (a <= 4-channel input: such launches are fp32 in, fp32 out, and then the layer's target is fp32)
+            c["thin"] = bool(bf16 and self.cls_batch is None and _thin(ly.dM, S, c["npix"], self.dgrad_two_target))
         def prof(table, route, splits, *head):         # (profiler kind, tag) -- the data gradient's tag: its tail, per launch
             kind, sfx = _ROUTE_PROF[table][route]
-            return kind + ("_bf16" if bf16 else ""), head + (self.dims[9:12], stride, reflect) + tuple(splits if v is None else v for v in sfx)
+            return kind + ("_bf16" if bf16 else ""), head + (self.dims[9:12], self.stride, ly.reflect) + tuple(splits if v is None else v for v in sfx)
         self.fwd_prof = prof("conv", self.fwd_route, self.g8_fwd_splits if self.g8_fwd else self.fwd_splits, "fwd", Cout, self.K, N * osp)
         self.dgrad_prof = prof("conv", self.dgrad_route, S)
         self.wgrad_prof = prof("wgrad", self.wgrad_route, self.wg_splits, "wgrad", Cout, self.K, N * osp)

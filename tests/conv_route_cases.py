@@ -1,6 +1,7 @@
 """The route table shared by tests/test_conv_routes_cpu.py (what each plan says) and tests/test_gpu_conv_routes.py (what is launched):
 layer geometries and knob settings with the route each pass takes, written down from the if-chains the route names replaced."""
 import contextlib
+import itertools
 
 from c2m_amd import ops
 
@@ -53,6 +54,21 @@ TABLE = [
 FWD_ROUTES = {"wino3d", "wino4", "wino", "k333_nc8", "s2_nc8", "g8", "patch_nc8", "igemm"}
 DGRAD_ROUTES = FWD_ROUTES | {"wino4_ring", "wino_ring", "igemm_batched"}
 WGRAD_ROUTES = {"k333_nc8", "nc8", "s2_nc8", "wino3d", "wino", "igemm"}
+
+
+def sweep():
+    """(input shape, weight shape, stride, pad, reflect, bf16, dgrad_rows) of ~20 000 layer geometries for the default knobs: every
+    route name of every pass is reached (tools/conv_plan_digest.py hashes their plans; tests/test_conv_routes_cpu.py reads them)."""
+    sizes = ((8, 16), (16, 32), (32, 64), (64, 128), (128, 256), (15, 33), (120, 250))
+    chans = (3, 16, 32, 34, 64, 128, 256)
+    flags = list(itertools.product((False, True), repeat=2))
+    k2d = (((1, 1), S1, (0, 0, 0)), ((3, 3), S1, P2), ((4, 4), S2, P2), ((7, 7), S1, (0, 3, 3)))
+    for N, Cin, Cout, hw, (k, stride, pad), (reflect, bf16) in itertools.product((1, 8, 40), chans, chans, sizes, k2d, flags):
+        yield (N, Cin) + hw, (Cout, Cin) + k, stride, pad, reflect, bf16, 32 if Cin == 34 else None
+    k3d = (((3, 3, 3), S1, P3), ((4, 4, 4), (2, 2, 2), P3), ((1, 3, 3), S1, P2))
+    for N, T, Cin, Cout, hw, (k, stride, pad), (reflect, bf16) in itertools.product((1, 8), (2, 3, 6), (16, 34, 64), (3, 32, 64), sizes[:5],
+                                                                                    k3d, flags):
+        yield (N, Cin, T) + hw, (Cout, Cin) + k, stride, pad, reflect, bf16, 32 if Cin == 34 else None
 
 
 @contextlib.contextmanager

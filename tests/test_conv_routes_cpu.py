@@ -1,24 +1,29 @@
 """The route names of a convolution plan (ops._ConvPlan.fwd_route / dgrad_route / wgrad_route; no GPU): the literal table of
 tests/conv_route_cases.py -- layer geometries and knob settings with the route each pass takes --, the operand
-precision every geom array of a plan carries, and the NC8-only predicates against their former spelling over the eligibility flags.
+precision every geom array of a plan carries, and the NC8-only predicates against their former spelling over the eligibility flags
+(both over the table's plans and the ~20 000 of conv_route_cases.sweep()).
 tests/test_gpu_conv_routes.py runs the small cases of the same table and ties each name to what is launched."""
 import itertools
 
 import torch
 
 from c2m_amd import ops
-from conv_route_cases import DGRAD_ROUTES, FWD_ROUTES, TABLE, WGRAD_ROUTES, knobs
+from conv_route_cases import DGRAD_ROUTES, FWD_ROUTES, TABLE, WGRAD_ROUTES, knobs, sweep
 
 
-def _plans():
+def _plans(with_sweep=True):
+    """(plan, bf16, routes the table expects or None): the table's rows, each built and read under its knobs, then the ~20 000
+    geometries of conv_route_cases.sweep() under the default knobs."""
     for xs, ws, stride, pad, reflect, bf16, rows, kn, want in TABLE:
         with knobs(kn):
             yield ops._ConvPlan(xs, ws, stride, pad, reflect, torch.device("cpu"), bf16, rows), bf16, want
+    for xs, ws, stride, pad, reflect, bf16, rows in sweep() if with_sweep else ():
+        yield ops._ConvPlan(xs, ws, stride, pad, reflect, torch.device("cpu"), bf16, rows), bf16, None
 
 
 def test_route_table():
     seen = [set(), set(), set()]
-    for pl, _, want in _plans():
+    for pl, _, want in _plans(with_sweep=False):
         assert (pl.fwd_route, pl.dgrad_route, pl.wgrad_route) == want, (pl.dims, pl.bf16)
         for s, r in zip(seen, want):
             s.add(r)
@@ -64,15 +69,13 @@ def _flags_fwd_reads_only_nc8(pl, need_w):
 
 def test_nc8_only_predicates_follow_the_flags():
     said_yes = 0
-    for xs, ws, stride, pad, reflect, bf16, rows, kn, _ in TABLE:
-        with knobs(kn):            # (the predicates read _NC8 / _NC8_GRAD themselves: evaluated under the plan's knobs)
-            pl = ops._ConvPlan(xs, ws, stride, pad, reflect, torch.device("cpu"), bf16, rows)
-            for need_x, need_w in itertools.product((False, True), repeat=2):
-                got = ops._bwd_reads_only_nc8(pl, need_x, need_w)
-                assert got == _flags_bwd_reads_only_nc8(pl, need_x, need_w), (pl.dims, bf16, need_x, need_w)
-                said_yes += got
-            for need_w in (False, True):
-                got = ops._fwd_reads_only_nc8(pl, need_w)
-                assert got == _flags_fwd_reads_only_nc8(pl, need_w), (pl.dims, bf16, need_w)
-                said_yes += got
+    for pl, bf16, _ in _plans():       # (the predicates read _NC8 / _NC8_GRAD themselves: evaluated under the plan's knobs)
+        for need_x, need_w in itertools.product((False, True), repeat=2):
+            got = ops._bwd_reads_only_nc8(pl, need_x, need_w)
+            assert got == _flags_bwd_reads_only_nc8(pl, need_x, need_w), (pl.dims, bf16, need_x, need_w)
+            said_yes += got
+        for need_w in (False, True):
+            got = ops._fwd_reads_only_nc8(pl, need_w)
+            assert got == _flags_fwd_reads_only_nc8(pl, need_w), (pl.dims, bf16, need_w)
+            said_yes += got
     assert said_yes > 20          # (the table holds layers of both kinds)
