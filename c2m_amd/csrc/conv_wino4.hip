@@ -12,16 +12,18 @@
 // One workgroup = 512 threads = 8 waves = ONE per CU (two waves per SIMD): 64 output channels x a 16x32 output region (4 x 8
 // tiles = the 32 MFMA columns) of one image.  Wave w: output-channel half wm = w & 1, frequency group fg = w >> 1 (frequencies
 // 9 fg .. 9 fg + 8): 9 x 16 = 144 accumulator registers.  Per 8-channel chunk:
-//   * the 8 x 18 x 34 input patch (LDS row pitch 40: conflict-free transform reads) arrives by LDS-DMA two chunks ahead (three buffers; wave w fetches channel w, the per-lane
-//     source offsets -- reflect / bounds resolved once -- sit in a 768-entry LDS table, read once into registers);
+//   * the 8 x 18 x 34 input patch (LDS row pitch 40: conflict-free transform reads) arrives by LDS-DMA two chunks ahead (three buffers; wave w fetches channel w, every lane
+//     resolves the reflect / bounds of its own twelve source offsets once, in registers);
 //   * thread (channel tk, tile tn, half h) transforms three rows of V = B^T d B of its 6x6 tile into V[xi][k][tile] in LDS
 //     (double buffered);
 //   * the U = G g G^T fragments come from L2 in a pre-packed order (c2m_wino4_filter_transform), 9 x 16 bytes per lane;
 //   * 36 MFMAs per wave.
 // Every wave interleaves its share of the next chunk's transform (column pass of one column pair per group of 12 MFMAs, row pass
-// at the end) and of the patch DMA with its own MFMAs (sched_group_barrier: 1 MFMA : 2 VALU).  The inverse transform goes through LDS in four passes of 16 output channels: raw accumulators
-// [xi][cout][tile] -> one thread per (cout, tile) computes A^T m A, adds the bias, applies the activation and stores four
-// 16-byte row segments (or per pixel into Y / Y_interior for the two-target data gradient of reflect-padded layers).
+// at the end) and of the patch DMA with its own MFMAs (sched_group_barrier: 1 MFMA : 2 VALU).  The inverse transform goes through LDS in two passes of 32 output channels over the
+// whole block (patches and V are dead by then): all eight waves write raw accumulators [xi][cout][tile], one barrier, then every thread
+// takes two (cout, tile) items -- A^T m A, ring terms, bias, activation -- and stores four 16-byte row segments each (or per pixel into
+// Y / Y_interior for the two-target data gradient of reflect-padded layers).  Four barriers behind the loop instead of nine, no wave
+// waiting while the others write (four passes of 16 channels with half of the waves idle in each: DESIGN 5.1).
 #include "common.h"
 #include "conv_types.h"
 #include <stdlib.h>
@@ -70,8 +72,9 @@ constexpr int W4_PPOS = W4_PH * W4_PITCH;             // 720 LDS positions per c
 constexpr int W4_ROWS = (W4_PPOS + 63) / 64;          // 12 DMA rows of 64 positions (the last one: 16 live lanes)
 constexpr int W4_PCS = 722;                           // channel stride of the patch in LDS (half of it odd: see above)
 constexpr int W4_PBUF = W4_CK * W4_PCS + 48;          // one patch buffer (floats); + the dead lanes of the last channel's last row
-constexpr int W4_TAB = W4_ROWS * 64;                  // entries of the source-offset table
 constexpr int W4_VBUF = 36 * W4_CK * 32;              // one V buffer (floats)
+constexpr int W4_LOOP = 3 * W4_PBUF + 2 * W4_VBUF;    // LDS floats of the K loop: three patch buffers + two V buffers (143 616 B)
+constexpr int W4_EPI = 36 * 32 * 32;                  // LDS floats of an epilogue pass: [xi][32 cout][32 tiles] (147 456 B)
 
 // Interpolation points 0, +-3/4, +-3/2, inf (tools/wino43_matrices.py): every coefficient of B^T and A^T is dyadic (exact in fp32), and
 // the fp32 error is a quarter of the classic 0, +-1, +-2, inf set's (tools/wino43_error.py; measured on the GPU: see DESIGN 5.5).
@@ -88,28 +91,35 @@ constexpr int W4_VBUF = 36 * W4_CK * 32;              // one V buffer (floats)
 
 // Phase timestamps of workgroup 0 (tuning builds only: python -m c2m_amd.build w4trace -DW4_TRACE; tools/trace_wino4.py): s_memtime at
 // four points of the first 16 intervals of every wave, kept in LDS (a global store would count in vmcnt) and copied out at the end.
+// W4_PSTAMP: sixteen more stamps per wave outside the K loop -- 0 source offsets ready, 1 first patch landed (wait + barrier),
+// 2 transform(0) done, 3 loop entry (patch 1 and U(0) complete), 4 loop left (last wait + barrier), 5 + 2 pass accumulators of the pass
+// written and visible (barrier), 6 + 2 pass inverse transform + stores of the pass issued; inside the last pass 13 first item's stores
+// issued, 14 second item's values ready (its stores still to come).
 #ifdef W4_TRACE
-__device__ unsigned long long w4_trace_buf[8 * 16 * 4 + 8 * 2];
+constexpr int W4_TRACE_N = 8 * 16 * 4 + 8 * 2 + 8 * 16;
+__device__ unsigned long long w4_trace_buf[W4_TRACE_N];
 #define W4_STAMP(i) do { if (blockIdx.x == 0 && lane == 0 && n < 16) sTr[(wave * 16 + n) * 4 + (i)] = clock64(); } while (0)
+#define W4_PSTAMP(i) do { if (blockIdx.x == 0 && lane == 0) sTr[8 * 16 * 4 + 8 * 2 + wave * 16 + (i)] = clock64(); } while (0)
 C2M_API int c2m_wino4_trace_read(unsigned long long* host) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(w4_trace_buf), sizeof(w4_trace_buf));
 }
 #else
 #define W4_STAMP(i) do { } while (0)
+#define W4_PSTAMP(i) do { } while (0)
 #endif
 
 __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
     // ONE LDS block with the DMA targets first: the LDS address of a buffer_load ... lds travels in M0, and only destinations
     // below 64 KB behaved (with the patches behind the 72 KB of V -- addresses 0x12000 ... 0x21000 -- results were intermittently
     // wrong and a launch faulted)
-    __shared__ __attribute__((aligned(16))) float smem[3 * W4_PBUF + W4_TAB + 2 * W4_VBUF];
+    __shared__ __attribute__((aligned(16))) float smem[W4_LOOP > W4_EPI ? W4_LOOP : W4_EPI];
 #ifdef W4_TRACE
-    __shared__ unsigned long long sTr[8 * 16 * 4 + 8 * 2];
+    __shared__ unsigned long long sTr[W4_TRACE_N];
     const unsigned long long t_begin = clock64();
+    if ((threadIdx.x & 63) < 16) sTr[8 * 16 * 4 + 8 * 2 + (threadIdx.x >> 6) * 16 + (threadIdx.x & 63)] = 0;
 #endif
 #define sP (smem)                                              /* input patches [buf][k][18][34] (+pad): 60 KB, LDS-DMA two chunks ahead */
-#define sVo (reinterpret_cast<unsigned*>(smem + 3 * W4_PBUF))  /* per patch position: byte offset inside X or C2M_OOB */
-#define sV (smem + 3 * W4_PBUF + W4_TAB)                       /* V[buf][xi][k][tile]; reused by the epilogue */
+#define sV (smem + 3 * W4_PBUF)                                /* V[buf][xi][k][tile] */
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave & 1, fg = wave >> 1;
@@ -129,10 +139,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
     const int oy0 = ry * W4_OR, ox0 = rx * W4_OC;
     const int nchunks = p.nchunks;
 
-    // ---- patch source offsets (fixed over the K loop)
+    // ---- patch source offsets (fixed over the K loop): lane l of every wave fetches positions dr * 64 + l of its channel, so each lane
+    // resolves its own twelve (reflect / bounds; byte offset inside X or C2M_OOB) in registers -- a shared 768-entry LDS table cost a
+    // barrier and twelve LDS round trips in front of the first DMA instruction of every workgroup
+    unsigned pvo[W4_ROWS];
     {
         const unsigned img_byte = (unsigned)(img * (int)p.in_sn) * 4u;
-        for (int pos = tid; pos < W4_TAB; pos += 512) {
+#pragma unroll
+        for (int dr = 0; dr < W4_ROWS; ++dr) {
+            const int pos = dr * 64 + lane;
             const int r = pos / W4_PITCH, c = pos % W4_PITCH;
             int iy = oy0 + p.iy0 + r, ix = ox0 + p.ix0 + c;
             if (p.reflect) {
@@ -140,10 +155,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
                 ix = ix < 0 ? -ix : ix; ix = ix >= p.Wi ? 2 * p.Wi - 2 - ix : ix;
             }
             const bool ok = pos < W4_PPOS && c < W4_PW && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            sVo[pos] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : C2M_OOB;
+            pvo[dr] = ok ? img_byte + (unsigned)(iy * p.in_sh + ix) * 4u : C2M_OOB;
         }
     }
-    __syncthreads();
+    W4_PSTAMP(0);
 
     const unsigned long xaddr = (unsigned long)p.X;
     const u32x4 rs = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, p.x_bytes, 0x00020000u};
@@ -151,11 +166,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
     // wave w fetches channel w of a chunk: twelve DMA rows of 64 positions.  A channel past K gets a zero-record descriptor (the
     // scalar offset is outside the hardware's range check); lanes past position 611 and positions outside the image carry an
     // out-of-range voffset and write zeros into the channel's own padding / halo.
-    // this lane's ten source offsets, read ONCE: fetched from the table in front of every DMA instruction they cost an LDS round
-    // trip each (ds_read -> wait -> DMA, ten times in a row at the start of every interval, in front of the matrix phase)
-    unsigned pvo[W4_ROWS];
-#pragma unroll
-    for (int dr = 0; dr < W4_ROWS; ++dr) pvo[dr] = sVo[dr * 64 + lane];
     auto load_patch = [&](int chunk, int buf, const int dr0 = 0, const int dr1 = W4_ROWS) __attribute__((always_inline)) {
 #ifdef W4_ZERO_RECORDS
         const int ch = chunk * W4_CK + wave;
@@ -362,12 +372,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
     load_u(0);
     asm volatile("s_waitcnt vmcnt(21)" ::: "memory");         // patch 0 has landed (patch 1 + U(0) may still be in flight)
     __syncthreads();
+    W4_PSTAMP(1);
     transform(0, 0);
+    W4_PSTAMP(2);
 #ifdef W4_FUSED
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // patch 1 and U(0) complete: the loop's counted waits assume a steady state
 #else
     asm volatile("s_waitcnt vmcnt(9)" ::: "memory");          // patch 1 (this wave's part) complete before the first barrier
 #endif
+    W4_PSTAMP(3);
     // Interval n: MFMAs of chunk n on V(n) / U(n); transform of chunk n + 1 (patch (n+1) % 3 -> V buffer (n+1) & 1); DMA of patch
     // n + 2 issued first so that it has the whole interval to land.  VMEM order per wave: DMA(n+2) x 12, later U(n+1) x 9.
     //   before the MFMAs:   vmcnt(12) -- U(n), issued in the previous interval, complete; the 12 DMA rows may be in flight
@@ -419,13 +432,20 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
 #pragma unroll
     for (int f = 0; f < 9; ++f) asm volatile("" :: "v"(ua[f]));
     __syncthreads();
+    W4_PSTAMP(4);
 
-    // ---- inverse transform: four passes of 16 output channels through LDS
-    float* __restrict__ sR = sV;                              // [xi][16 cout][32 tiles]
-    const int etile = tid & 31, ecl = tid >> 5;               // epilogue role: one (cout, tile) per thread
+    // ---- inverse transform: two passes of 32 output channels through LDS.  Behind the wait + barrier above the patch buffers (the
+    // DMA rows fetched past the last chunk have landed) and both V buffers are dead: a pass takes the WHOLE block.  Pass hf: every wave
+    // writes accumulator registers 8 hf .. 8 hf + 7 of its nine frequencies (rows 16 hf .. 16 hf + 15 of its 32-row half wm) -- all
+    // eight waves write at once, one barrier -- then every thread inverts two (cout, tile) items, one per half wm.
+    float* __restrict__ sR = smem;                            // [xi][32 cout = (wm, 16 rows)][32 tiles]
+    // the epilogue's thread index from the hardware lane count, not from tid: derived from tid, 4 ety / 4 etx are the transform role's
+    // subexpressions and stayed live -- in scratch -- across the K loop
+    const int elane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int etile = elane & 31, ecl = 2 * wave + (elane >> 5);     // epilogue role: (cout row ecl of both halves, tile) per thread
     const int ety = etile >> 3, etx = etile & 7;
     const int oyb = oy0 + 4 * ety, oxb = ox0 + 4 * etx;
-    // the four passes' bias values up front: loaded inside a pass, the ~2 000-cycle round trip sat in front of its stores four times
+    // the four items' bias values up front (index 2 wm + hf): loaded inside a pass, the ~2 000-cycle round trip sat in front of its stores
     float bias4[4];
 #pragma unroll
     for (int pass = 0; pass < 4; ++pass) {
@@ -433,110 +453,137 @@ __global__ __launch_bounds__(512, 2) void conv_wino4_kernel(const Wino4P p) {
         bias4[pass] = (p.bias && co < p.M) ? p.bias[co] : 0.f;
     }
 #pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int pwm = pass >> 1, hf = pass & 1;
-        __syncthreads();
-        if (wm == pwm) {
+    for (int hf = 0; hf < 2; ++hf) {
+        if (hf) __syncthreads();                              // every item of pass 0 has been read
 #pragma unroll
-            for (int f = 0; f < 9; ++f)
+        for (int f = 0; f < 9; ++f)
 #pragma unroll
-                for (int rr = 0; rr < 8; ++rr) {
-                    const int rowl = (rr & 3) + 8 * (rr >> 2) + 4 * (lane >> 5);
-                    sR[((9 * fg + f) * 16 + rowl) * 32 + (lane & 31)] = hf ? acc[f][8 + rr] : acc[f][rr];
-                }
-        }
-        __syncthreads();
-        const int cout = mt * 64 + pwm * 32 + hf * 16 + ecl;
-        float y[4][4];
-        {
-            float s[6][4];                                     // m A  (columns 6 -> 4)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const float* __restrict__ q = sR + ((6 * i) * 16 + ecl) * 32 + etile;
-                const float m0 = q[0], m1 = q[16 * 32], m2 = q[2 * 16 * 32], m3 = q[3 * 16 * 32], m4 = q[4 * 16 * 32], m5 = q[5 * 16 * 32];
-                const float pp = m1 + m2, nn = m1 - m2, PP = m3 + m4, NN = m3 - m4;
-                // A^T = [1 1 1 1 1 0; 0 3/4 -3/4 3/2 -3/2 0; 0 9/16 9/16 9/4 9/4 0; 0 27/64 -27/64 27/8 -27/8 1]
-                s[i][0] = m0 + pp + PP; s[i][1] = 0.75f * nn + 1.5f * NN; s[i][2] = 0.5625f * pp + 2.25f * PP;
-                s[i][3] = 0.421875f * nn + 3.375f * NN + m5;
+            for (int rr = 0; rr < 8; ++rr) {
+                const int rowl = (rr & 3) + 8 * (rr >> 2) + 4 * (elane >> 5);
+                sR[((9 * fg + f) * 32 + wm * 16 + rowl) * 32 + etile] = hf ? acc[f][8 + rr] : acc[f][rr];
             }
+        __syncthreads();
+        W4_PSTAMP(5 + 2 * hf);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {                      // A^T (rows 6 -> 4)
-                const float pp = s[1][c] + s[2][c], nn = s[1][c] - s[2][c], PP = s[3][c] + s[4][c], NN = s[3][c] - s[4][c];
-                y[0][c] = s[0][c] + pp + PP; y[1][c] = 0.75f * nn + 1.5f * NN; y[2][c] = 0.5625f * pp + 2.25f * PP;
-                y[3][c] = 0.421875f * nn + 3.375f * NN + s[5][c];
+        for (int pwm = 0; pwm < 2; ++pwm) {
+            const int pass = 2 * pwm + hf;
+            const int cout = mt * 64 + pwm * 32 + hf * 16 + ecl;
+            float y[4][4];
+            {
+                float s[6][4];                                     // m A  (columns 6 -> 4)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) {
+                    const float* __restrict__ q = sR + ((6 * i) * 32 + pwm * 16 + ecl) * 32 + etile;
+                    const float m0 = q[0], m1 = q[32 * 32], m2 = q[2 * 32 * 32], m3 = q[3 * 32 * 32], m4 = q[4 * 32 * 32], m5 = q[5 * 32 * 32];
+                    const float pp = m1 + m2, nn = m1 - m2, PP = m3 + m4, NN = m3 - m4;
+                    // A^T = [1 1 1 1 1 0; 0 3/4 -3/4 3/2 -3/2 0; 0 9/16 9/16 9/4 9/4 0; 0 27/64 -27/64 27/8 -27/8 1]
+                    s[i][0] = m0 + pp + PP; s[i][1] = 0.75f * nn + 1.5f * NN; s[i][2] = 0.5625f * pp + 2.25f * PP;
+                    s[i][3] = 0.421875f * nn + 3.375f * NN + m5;
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {                      // A^T (rows 6 -> 4)
+                    const float pp = s[1][c] + s[2][c], nn = s[1][c] - s[2][c], PP = s[3][c] + s[4][c], NN = s[3][c] - s[4][c];
+                    y[0][c] = s[0][c] + pp + PP; y[1][c] = 0.75f * nn + 1.5f * NN; y[2][c] = 0.5625f * pp + 2.25f * PP;
+                    y[3][c] = 0.421875f * nn + 3.375f * NN + s[5][c];
+                }
             }
-        }
-        if (cout < p.M) {
-            const float bb = bias4[pass];
-            const float* __restrict__ rb = p.R ? p.R + ((long)img * p.M + cout) * 4 * p.r_l : nullptr;
+            if (pass == 3) W4_PSTAMP(14);
+            if (cout < p.M) {
+                const float bb = bias4[pass];
+                // the item in three straight blocks -- ring terms, bias + activation, stores -- with ONE uniform branch each: taken per
+                // row (and the activation's switch per element) the branches, not the arithmetic, were most of an item's 2 400 cycles
+                if (p.R) {                                         // uniform: the ring terms of the reflect data gradient
+                    const float* __restrict__ rb = p.R + ((long)img * p.M + cout) * 4 * p.r_l;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int oy = oyb + r;
-                if (oy >= p.Ho) continue;
-                if (rb) {                                      // uniform: the ring terms of the reflect data gradient
-                    if (oy == 1 || oy == p.Ho - 2) {
-                        const float* __restrict__ rr = rb + (oy == 1 ? 0 : p.r_l) + oxb;
+                    for (int r = 0; r < 4; ++r) {
+                        const int oy = oyb + r;
+                        if (oy >= p.Ho) continue;
+                        if (oy == 1 || oy == p.Ho - 2) {
+                            const float* __restrict__ rr = rb + (oy == 1 ? 0 : p.r_l) + oxb;
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) if (oxb + c < p.Wo) y[r][c] += rr[c];
-                    }
-                    if (oxb <= 1 && oxb + 3 >= 1) {
-                        const float v = rb[2 * p.r_l + oy];
+                            for (int c = 0; c < 4; ++c) if (oxb + c < p.Wo) y[r][c] += rr[c];
+                        }
+                        if (oxb <= 1 && oxb + 3 >= 1) {
+                            const float v = rb[2 * p.r_l + oy];
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) if (oxb + c == 1) y[r][c] += v;
-                    }
-                    if (oxb <= p.Wo - 2 && oxb + 3 >= p.Wo - 2) {
-                        const float v = rb[3 * p.r_l + oy];
+                            for (int c = 0; c < 4; ++c) if (oxb + c == 1) y[r][c] += v;
+                        }
+                        if (oxb <= p.Wo - 2 && oxb + 3 >= p.Wo - 2) {
+                            const float v = rb[3 * p.r_l + oy];
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) if (oxb + c == p.Wo - 2) y[r][c] += v;
+                            for (int c = 0; c < 4; ++c) if (oxb + c == p.Wo - 2) y[r][c] += v;
+                        }
                     }
                 }
-                if (p.act == C2M_ACT_NONE) {                   // one uniform branch per row instead of a switch per element
+                if (p.act == C2M_ACT_NONE) {                       // (rows past Ho are computed and never stored)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) y[r][c] += bb;
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) y[r][c] += bb;
                 } else if (p.act == C2M_ACT_LRELU) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) { const float v = y[r][c] + bb; y[r][c] = v > 0.f ? v : p.slope * v; }
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) { const float v = y[r][c] + bb; y[r][c] = v > 0.f ? v : p.slope * v; }
                 } else {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) y[r][c] = c2m_act(y[r][c] + bb, p.act, p.slope);
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) y[r][c] = c2m_act(y[r][c] + bb, p.act, p.slope);
                 }
-                float* __restrict__ yb0 = p.Y + p.out_off + (long)img * p.out_sn + (long)cout * p.out_sc + (long)oy * p.out_sh + oxb;
                 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-                const f32x4u vv = {y[r][0], y[r][1], y[r][2], y[r][3]};
-                const int yi = oy - p.lo_y, xi0 = oxb - p.lo_x;
-                const bool row_in = p.Y2 && (unsigned)yi < (unsigned)p.ext_y;
-                // two-target launches: a 4-pixel group that lies entirely inside the interior goes to Y_interior with one 16-byte
-                // store, one entirely outside it to Y (the pad ring); only groups that straddle the interior's edge go per pixel
-                const bool all_in = row_in && xi0 >= 0 && xi0 + 3 < p.ext_x;
-                const bool all_out = !row_in || xi0 + 3 < 0 || xi0 >= p.ext_x;
-                if (oxb + 3 < p.Wo && (!p.Y2 || all_out)) {
-                    *reinterpret_cast<f32x4u*>(yb0) = vv;
-                } else if (oxb + 3 < p.Wo && all_in) {
-                    *reinterpret_cast<f32x4u*>(p.Y2 + (long)img * p.y2_sn + (long)cout * p.y2_sc + (long)yi * p.y2_sh + xi0) = vv;
+                float* __restrict__ yb = p.Y + p.out_off + (long)img * p.out_sn + (long)cout * p.out_sc + (long)oyb * p.out_sh + oxb;
+                if (!p.Y2 && oyb + 3 < p.Ho && oxb + 3 < p.Wo) {
+                    // single target, the whole 4 x 4 tile inside the output: four plain 16-byte row stores, no per-row decisions
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const f32x4u vv = {y[r][0], y[r][1], y[r][2], y[r][3]};
+                        *reinterpret_cast<f32x4u*>(yb + (long)r * p.out_sh) = vv;
+                    }
                 } else {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (oxb + c >= p.Wo) continue;
-                        const int xi = oxb + c - p.lo_x;
-                        if (row_in && (unsigned)xi < (unsigned)p.ext_x)
-                            p.Y2[(long)img * p.y2_sn + (long)cout * p.y2_sc + (long)yi * p.y2_sh + xi] = y[r][c];
-                        else
-                            yb0[c] = y[r][c];
+                    for (int r = 0; r < 4; ++r) {
+                        const int oy = oyb + r;
+                        if (oy >= p.Ho) continue;
+                        float* __restrict__ yb0 = yb + (long)r * p.out_sh;
+                        const f32x4u vv = {y[r][0], y[r][1], y[r][2], y[r][3]};
+                        const int yi = oy - p.lo_y, xi0 = oxb - p.lo_x;
+                        const bool row_in = p.Y2 && (unsigned)yi < (unsigned)p.ext_y;
+                        // two-target launches: a 4-pixel group that lies entirely inside the interior goes to Y_interior with one 16-byte
+                        // store, one entirely outside it to Y (the pad ring); only groups that straddle the interior's edge go per pixel
+                        const bool all_in = row_in && xi0 >= 0 && xi0 + 3 < p.ext_x;
+                        const bool all_out = !row_in || xi0 + 3 < 0 || xi0 >= p.ext_x;
+                        if (oxb + 3 < p.Wo && (!p.Y2 || all_out)) {
+                            *reinterpret_cast<f32x4u*>(yb0) = vv;
+                        } else if (oxb + 3 < p.Wo && all_in) {
+                            *reinterpret_cast<f32x4u*>(p.Y2 + (long)img * p.y2_sn + (long)cout * p.y2_sc + (long)yi * p.y2_sh + xi0) = vv;
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                if (oxb + c >= p.Wo) continue;
+                                const int xi = oxb + c - p.lo_x;
+                                if (row_in && (unsigned)xi < (unsigned)p.ext_x)
+                                    p.Y2[(long)img * p.y2_sn + (long)cout * p.y2_sc + (long)yi * p.y2_sh + xi] = y[r][c];
+                                else
+                                    yb0[c] = y[r][c];
+                            }
+                        }
                     }
                 }
             }
+            if (pass == 1) W4_PSTAMP(13);
         }
+        W4_PSTAMP(6 + 2 * hf);
     }
 #ifdef W4_TRACE
     if (blockIdx.x == 0 && lane == 0) { sTr[8 * 16 * 4 + wave * 2] = t_begin; sTr[8 * 16 * 4 + wave * 2 + 1] = clock64(); }
     __syncthreads();
     if (blockIdx.x == 0)
-        for (int i = tid; i < 8 * 16 * 4 + 8 * 2; i += 512) w4_trace_buf[i] = sTr[i];
+        for (int i = tid; i < W4_TRACE_N; i += 512) w4_trace_buf[i] = sTr[i];
 #endif
 }
 
 #undef sP
-#undef sVo
 #undef sV
 
 // Filter transform U = G g G^T (6x6), G = [[64/81,0,0],[-128/243,-32/81,-8/27],[-128/243,32/81,-8/27],[32/243,16/81,8/27],[32/243,-16/81,8/27],[0,0,1]],
