@@ -17,6 +17,10 @@
 //                           1 / max(1, |residual of that patch at this pixel|).  No atomics.  With shift > 0 it writes the flow of a
 //                           coarser level straight at the size of level 0 (2^shift * f[y >> shift][x >> shift]).
 //
+//   fl_patch_match_kernel   the optional seed of the coarsest level (at the end of this file): one wave per patch tries
+//                           every integer displacement within a radius whose window lies inside b and keeps the cheapest; its
+//                           records are densified as the search's are, and the search starts from that flow.
+//
 // Segment guide: the <true> instantiations of the search and the densify read the level-0 id map of frame a
 // (level l reads it at (y << l, x << l)).  A patch sum runs over the lanes whose id is that of the patch centre, a pixel is
 // averaged over the covering patches whose centre has its id; a record gains the lane count n as a fourth float.  The <false>
@@ -387,4 +391,148 @@ C2M_API int c2m_flow_densify_guided(const float* ia, const float* ib, long image
     if (!fl_level_ok(N, h, w) || !fl_seg_ok(segments, segment_elems, N, level, H, W, h, w)) return (int)hipErrorInvalidValue;
     return fl_densify(ia, ib, image_elems, records, record_elems, flow, flow_elems, N, h, w, shift, Ho, Wo, segments, level, H, W,
                       stream);
+}
+
+// ------------------------------------------------------------------------------------------------ block-matching seed
+// fl_patch_match_kernel (tests/flow_seed_np.py restates it): the start of the coarsest level's search for fast
+// motion.  One wave per patch, the patches and the loop of fl_patch_search_kernel.  A patch tries every integer displacement
+// (dx, dy) in [-R, R]^2 whose 8 x 8 window lies wholly inside b's level, 0 <= ox + dx <= w - 8 and 0 <= oy + dy <= h - 8, and
+// takes the one with the smallest key (cost, dx^2 + dy^2, dy, dx): a total order, so the choice does not depend on which lane
+// held which candidate.  cost = sum(((J - mJ) - Tm)^2) with mJ = sum(J) / 64; BOTH SUMS RUN OVER THE 64 PIXELS IN RASTER ORDER
+// (py-major), one term after the other, from 0.f.  T, gx, gy, mean(T), Tm and det are those of the search (the same
+// wave_sum_all); a patch with det <= its threshold has the one candidate (0, 0).  Guided: the sums run over the pixels with the
+// id of the patch centre (the others add 0.f), means divide by n, the record carries n.  Record: (dx, dy, mJ - mean(T)).
+//
+// LDS, private to a wave: Tm [64] and the (8 + 2 R)^2 window of b around the patch, row stride 8 + 2 R: (64 + 24 * 24) floats
+// = 2560 B a wave, 10 KB a workgroup.  Lane k evaluates the candidates k, k + 64, ... of the (2 R + 1)^2 (dy-major); the lanes
+// of a wave read window cells one apart (a 2-way bank conflict where a candidate row wraps: R = 4 reads 9 cells a row of 16),
+// Tm[k] is one address for all lanes (a broadcast).  The loop is workgroup-uniform (a wave past the last patch stages and
+// computes nothing) so that the two barriers of an item are reached by all four waves.
+#define C2M_FLOW_MATCH_MAX_R 8
+#define C2M_FLOW_MATCH_SIDE (C2M_FLOW_PATCH + 2 * C2M_FLOW_MATCH_MAX_R)
+#define C2M_FLOW_MATCH_LDS (64 + C2M_FLOW_MATCH_SIDE * C2M_FLOW_MATCH_SIDE)
+
+struct FlPmP {
+    const float* ia; const float* ib; float* rec;
+    int h, w, npy, npx, R;
+    long waves;                                                                 // N * npy * npx: one wave each
+};
+
+template <bool G>
+__global__ __launch_bounds__(256) void fl_patch_match_kernel(const FlPmP p, const FlSegP g) {
+    __shared__ float lds[4 * C2M_FLOW_MATCH_LDS];
+    const int lane = threadIdx.x & 63, py = lane >> 3, px = lane & 7;
+    const int h = p.h, w = p.w, R = p.R, D = 2 * R + 1, S = C2M_FLOW_PATCH + 2 * R;
+    float* __restrict__ tm = lds + (threadIdx.x >> 6) * C2M_FLOW_MATCH_LDS;
+    float* __restrict__ win = tm + 64;
+    const long nwaves = (long)gridDim.x * 4;
+    for (long base = (long)blockIdx.x * 4; base < p.waves; base += nwaves) {                      // workgroup-uniform
+        const long i = base + (threadIdx.x >> 6);
+        const bool live = i < p.waves;                                          // wave-uniform
+        int ox = 0, oy = 0;
+        long n = 0;
+        bool in = true, ok = false;
+        float cnt = 64.f, mT = 0.f;
+        __syncthreads();                                                        // the previous item's LDS has been read
+        if (live) {
+            const int jx = (int)(i % p.npx);
+            const long t = i / p.npx;
+            const int jy = (int)(t % p.npy);
+            n = t / p.npy;
+            ox = min(C2M_FLOW_STRIDE * jx, w - C2M_FLOW_PATCH); oy = min(C2M_FLOW_STRIDE * jy, h - C2M_FLOW_PATCH);
+            const int x = ox + px, y = oy + py;                                 // inside the image: ox + 7 <= w - 1
+            const float* __restrict__ A = p.ia + n * ((long)h * w);
+            const float* __restrict__ B = p.ib + n * ((long)h * w);
+            const float* __restrict__ row = A + (long)y * w;
+            const float T = row[x];
+            const float gx = 0.5f * (row[min(x + 1, w - 1)] - row[max(x - 1, 0)]);
+            const float gy = 0.5f * (A[(long)min(y + 1, h - 1) * w + x] - A[(long)max(y - 1, 0) * w + x]);
+            float det_min = C2M_FLOW_DET_MIN;
+            if constexpr (G) {
+                in = g.at(n, y, x) == g.at(n, oy + 3, ox + 3);
+                const int k = wave_count(in);
+                cnt = (float)k;
+                det_min = C2M_FLOW_DET_MIN * ((float)(k * k) / 4096.f);
+            }
+            auto part = [&](float v) { if constexpr (G) return in ? v : 0.f; else return v; };
+            mT = wave_sum_all(part(T));
+            if constexpr (G) mT = mT / cnt; else mT = mT * 0.015625f;
+            const float a = wave_sum_all(part(gx * gx)), b = wave_sum_all(part(gx * gy)), c = wave_sum_all(part(gy * gy));
+            ok = a * c - b * b > det_min;                                       // wave-uniform: every lane holds lane 0's sums
+            tm[lane] = T - mT;
+            // the window cell (wy, wx) is b's pixel (oy - R + wy, ox - R + wx).  NO COORDINATE IS CLAMPED: a cell outside the image
+            // is neither loaded nor, below, read, because a candidate whose window is not wholly inside the image is skipped
+            for (int q = lane; q < S * S; q += 64) {
+                const int wy = q / S, wx = q - wy * S, by = oy - R + wy, bx = ox - R + wx;
+                if (by >= 0 && by < h && bx >= 0 && bx < w) win[q] = B[(long)by * w + bx];
+            }
+        }
+        __syncthreads();
+        if (!live) continue;                                                    // workgroup-uniform loop: the barriers are above
+        const unsigned long long members = G ? __ballot(in) : ~0ull;            // wave-uniform: bit k = pixel k carries the sums
+        float best = INFINITY, best_mj = 0.f;
+        int tie = INT_MAX;                                                      // (dx^2 + dy^2) << 10 | (dy + 8) << 5 | (dx + 8)
+        for (int cand = lane; cand < D * D; cand += 64) {
+            const int dy = cand / D - R, dx = cand - (dy + R) * D - R;
+            if (ox + dx < 0 || ox + dx > w - C2M_FLOW_PATCH || oy + dy < 0 || oy + dy > h - C2M_FLOW_PATCH) continue;
+            if (!ok && (dx | dy) != 0) continue;                                // det <= threshold: (0, 0) alone
+            // rows dy + R .. dy + R + 7 and columns dx + R .. dx + R + 7 of the window: inside [0, S) since |dx|, |dy| <= R,
+            // and cells that were loaded, since the displaced patch is inside the image
+            const float* __restrict__ J = win + (dy + R) * S + (dx + R);
+            float sj = 0.f;
+            for (int k = 0; k < 64; ++k) {                                      // raster order
+                const float v = J[(k >> 3) * S + (k & 7)];
+                if constexpr (G) sj += ((members >> k) & 1) ? v : 0.f; else sj += v;
+            }
+            float mj;
+            if constexpr (G) mj = sj / cnt; else mj = sj * 0.015625f;
+            float cost = 0.f;
+            for (int k = 0; k < 64; ++k) {                                      // raster order
+                const float d = (J[(k >> 3) * S + (k & 7)] - mj) - tm[k];
+                if constexpr (G) cost += ((members >> k) & 1) ? d * d : 0.f; else cost += d * d;
+            }
+            if (!(cost < INFINITY)) cost = INFINITY;                            // a NaN or an overflow: never below another cost
+            const int key = ((dx * dx + dy * dy) << 10) | ((dy + 8) << 5) | (dx + 8);
+            if (cost < best || (cost == best && key < tie)) { best = cost; tie = key; best_mj = mj; }
+        }
+        wave_min_key_all(best, tie, best_mj);                                   // (0, 0) is always a candidate: tie < INT_MAX
+        if (lane == 0) {
+            float* __restrict__ o = p.rec + i * (G ? 4 : 3);
+            o[0] = (float)((tie & 31) - 8); o[1] = (float)(((tie >> 5) & 31) - 8); o[2] = best_mj - mT;
+            if constexpr (G) o[3] = cnt;
+        }
+    }
+}
+
+// ids NULL: the unguided match (records of 3 floats); else the guided one (4 floats)
+static int fl_patch_match(const float* ia, const float* ib, long image_elems, float* records, long record_elems, int N, int h,
+                          int w, int radius, const int32_t* ids, int level, int H, int W, void* stream) {
+    if (!fl_level_ok(N, h, w) || radius < 1 || radius > C2M_FLOW_MATCH_MAX_R) return (int)hipErrorInvalidValue;
+    if (N == 0) return 0;
+    FlPmP p;
+    p.ia = ia; p.ib = ib; p.rec = records;
+    p.h = h; p.w = w; p.npy = fl_patches(h); p.npx = fl_patches(w); p.R = radius;
+    p.waves = (long)N * p.npy * p.npx;
+    if (!ia || !ib || !records || image_elems < (long)N * h * w || record_elems < p.waves * (ids ? 4 : 3) ||
+        !c2m_aligned(4, ia, ib, records))
+        return (int)hipErrorInvalidValue;
+    const FlSegP g = {ids, level, W, (long)H * W};
+    const dim3 grid(c2m_grid(p.waves * 64, 256));
+    if (ids) hipLaunchKernelGGL(fl_patch_match_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
+    else hipLaunchKernelGGL(fl_patch_match_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p, g);
+    return (int)hipGetLastError();
+}
+
+C2M_API int c2m_flow_patch_match(const float* ia, const float* ib, long image_elems, float* records, long record_elems, int N,
+                                 int h, int w, int radius, void* stream) {
+    C2M_ENTER();
+    return fl_patch_match(ia, ib, image_elems, records, record_elems, N, h, w, radius, nullptr, 0, 0, 0, stream);
+}
+
+C2M_API int c2m_flow_patch_match_guided(const float* ia, const float* ib, long image_elems, float* records, long record_elems,
+                                        int N, int h, int w, int radius, const int32_t* segments, long segment_elems, int level,
+                                        int H, int W, void* stream) {
+    C2M_ENTER();
+    if (!fl_level_ok(N, h, w) || !fl_seg_ok(segments, segment_elems, N, level, H, W, h, w)) return (int)hipErrorInvalidValue;
+    return fl_patch_match(ia, ib, image_elems, records, record_elems, N, h, w, radius, segments, level, H, W, stream);
 }

@@ -1,4 +1,5 @@
-// Wave64 primitives shared by the c2m_amd kernels (gfx950): sums, ordered ranks and the merge of equal keys before an atomic.
+// Wave64 primitives shared by the c2m_amd kernels (gfx950): sums, ordered ranks, the smallest key and the merge of equal keys
+// before an atomic.
 // Every function here is WAVE-WIDE (ballots and shuffles read all 64 lanes) or, where its name says 256, workgroup-wide: whole
 // waves (whole workgroups) must reach the call.  A lane that has nothing to contribute passes pred / valid = false; it never
 // leaves a loop or returns before the call.  Thread ids are 1-D (threadIdx.x).  Included by common.h.
@@ -53,6 +54,19 @@ __device__ __forceinline__ int block_rank_256(bool pred, int* smem4, int& total)
     for (int w = 0; w < wave; ++w) rank += smem4[w];
     total = smem4[0] + smem4[1] + smem4[2] + smem4[3];
     return rank;
+}
+
+// ------------------------------------------------------------------------------------------------ the smallest key of a wave
+// The lexicographically smallest (k, tie) over the 64 lanes and the value v of the lane that holds it, in every lane.  k must not
+// be NaN.  (k, tie) is a total order: lanes with one (k, tie) must hold one v, and then the result does not depend on the order
+// of the exchange.
+__device__ __forceinline__ void wave_min_key_all(float& k, int& tie, float& v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float k2 = __shfl_xor(k, o, 64), v2 = __shfl_xor(v, o, 64);
+        const int t2 = __shfl_xor(tie, o, 64);
+        if (k2 < k || (k2 == k && t2 < tie)) { k = k2; tie = t2; v = v2; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ distinct keys of a wave

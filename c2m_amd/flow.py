@@ -9,11 +9,14 @@ it drops into `train.compute_flow`, into `tracking.tracked_batch`'s inputs and i
 The algorithm is a coarse-to-fine inverse search over 8 x 8 patches at stride 4 (one wave64 per patch), a fixed number of steps
 per patch and a weighted average of the patches that cover a pixel.  `refine=True` adds a variational refinement of every level's
 flow (csrc/flow_refine.hip; off by default).  A motion of more than about 8 px at the coarsest level (25 px at
-128 x 256, four levels) is out of range of ONE search; frames of a clip that are further apart get their flow from the flows
-between consecutive frames, chained (`chain_flows`, `clip_flows`, `ClassicFlow(chain=True)`; csrc/flow_chain.hip; DESIGN.md
-4.2n).  `segments=` (the int32 instance ids of frame a) keeps the motion of one id out of the estimate of another: patch sums,
-the average over patches and the refinement's smoothness stop at id borders (DESIGN.md 4.2p).  Nothing here has weights;
-nothing is differentiated.  There is no CPU path: a tensor that is not on a HIP device raises.
+128 x 256, four levels) is out of range of ONE search that starts at zero flow.  `seed=` starts the coarsest level's search
+from the best of the integer displacements within a radius (4 by default, at most 8) of every patch, found by block matching
+(`patch_match`; DESIGN.md 4.2q, with the measured limits; off by default): fast motion between two consecutive frames.
+Frames of a clip that are further apart get their flow from the flows between consecutive frames, chained (`chain_flows`,
+`clip_flows`, `ClassicFlow(chain=True)`; csrc/flow_chain.hip).  `segments=` (the int32 instance ids of frame a)
+keeps the motion of one id out of the estimate of another: patch sums, the average over patches and the refinement's
+smoothness stop at id borders.  Nothing here has weights; nothing is differentiated.  There is no CPU path: a
+tensor that is not on a HIP device raises.
 """
 import torch
 import torch.nn as nn
@@ -24,6 +27,7 @@ PATCH, STRIDE, MAX_LEVELS = 8, 4, 7
 REFINE_DEFAULTS = dict(alpha=20., delta=5., gamma=10., outer=5, sor=5, omega=1.6)      # OpenCV's DIS defaults; images on 0..255
 SOR_CAP = 5                                                   # the iterate kernel's tile has a halo of 2 * sor <= 10 pixels
 CHAIN_CAP = 16                                                # the most steps one chain_flows call follows
+SEED_RADIUS, SEED_CAP = 4, 8                                  # block matching at the coarsest level: default and largest radius
 
 
 def pyramid_sizes(H, W, levels=None):
@@ -145,6 +149,39 @@ def patch_search(ia, ib, init=None, iters=12, out=None, segments=None, level=0):
     return rec
 
 
+def patch_match(ia, ib, radius=SEED_RADIUS, out=None, segments=None, level=0):
+    """The block-matching seed of one level: ia, ib [N,h,w] fp32 -> records [N,npy,npx,3] = (dx, dy, mean(J) -
+    mean(T)) per patch, (dx, dy) the integer displacement in [-radius, radius]^2 (1 <= radius <= SEED_CAP) with the smallest
+    (cost, dx^2 + dy^2, dy, dx) among those whose 8 x 8 window lies inside ib; `densify` takes them.  segments, level: as in
+    patch_search, records [N,npy,npx,4].  ONE launch on the current stream."""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= SEED_CAP:
+        raise ValueError(f"radius must be an int 1 .. {SEED_CAP}, got {radius!r}")
+    ia, ib = _level_images(ia, ib)
+    N, h, w = ia.shape
+    segments = _segment_ids(segments, N, h, w, level, ia.device)
+    npy, npx = len(patch_origins(h)), len(patch_origins(w))
+    rec = torch.empty(N, npy, npx, 3 if segments is None else 4, device=ia.device, dtype=torch.float32) if out is None else out
+    if segments is not None:
+        _lib.check(_lib.lib().c2m_flow_patch_match_guided(
+            ops._p(ia), ops._p(ib), ia.numel(), ops._p(rec), rec.numel(), N, h, w, radius, ops._p(segments), segments.numel(),
+            int(level), segments.shape[1], segments.shape[2], ops._stream()), "flow_patch_match_guided")
+        return rec
+    _lib.check(_lib.lib().c2m_flow_patch_match(ops._p(ia), ops._p(ib), ia.numel(), ops._p(rec), rec.numel(), N, h, w, radius,
+                                               ops._stream()), "flow_patch_match")
+    return rec
+
+
+def seed_radius(seed):
+    """None / False -> None (no seed); True -> SEED_RADIUS; an int 1 .. SEED_CAP -> that radius; anything else raises."""
+    if seed is None or seed is False:
+        return None
+    if seed is True:
+        return SEED_RADIUS
+    if not isinstance(seed, int) or not 1 <= seed <= SEED_CAP:
+        raise ValueError(f"seed must be None, a bool or an int 1 .. {SEED_CAP} (the radius), got {seed!r}")
+    return seed
+
+
 def densify(ia, ib, records, shift=0, out_size=None, out=None, segments=None, level=0):
     """Step 7 for one level: the dense flow [N,2,h,w] from the patch records [N,npy,npx,3].  shift, out_size: write
     2**shift * flow[y >> shift, x >> shift] at out_size = (Ho, Wo) instead (a coarser level brought to level 0).  segments (as
@@ -263,7 +300,7 @@ def refine_flow(ia, ib, flow, alpha=20., delta=5., gamma=10., outer=5, sor=5, om
     return _refine_level(ia, ib, flow, p, _refine_workspace(N, h, w, ia.device), out, segments=segments, level=level)
 
 
-def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine=None, segments=None):
+def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine=None, segments=None, seed=None):
     """Flow a -> b of N image pairs -> [N,2,H,W] fp32 pixels (channel 0 = x; a(x) ~ b(x + flow(x))).
 
     a, b [N,3,H,W] fp32 or bf16 on the device, H, W >= 8, values in value_range = (lo, hi).  levels: at most that many pyramid
@@ -274,10 +311,14 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine
     segments: None, or the int32 ids [N,H,W] of frame a (instance ids; any integer is an id): the patch sums, the average over
     patches and the refinement's smoothness stop at id borders, which keeps the motion edge of an object sharp (DESIGN.md 4.2p;
     the same number of launches).  One id everywhere gives the bits of segments=None.
-    1 + 2 * (levels - finest) launches on the current stream whatever N is (1 + (3 + outer) * (levels - finest) with refinement),
-    no synchronisation, no copy to the host; the result is bit-repeatable and that of a pair does not depend on the other pairs
-    of the call.  No gradient flows through it."""
-    rp = refine_params(refine)
+    seed: None / False: the coarsest level's search starts at zero flow; True, or an int 1 .. SEED_CAP: from the densified
+    result of `patch_match` with radius SEED_RADIUS (that radius), which brings a motion of up to the radius at the coarsest
+    level (32 px at 128 x 256 with the default) into range; the 8 px of the search's reset then count from the seed (DESIGN.md
+    4.2q has what it recovers and what it does not).
+    1 + 2 * (levels - finest) launches on the current stream whatever N is (1 + (3 + outer) * (levels - finest) with refinement;
+    two more with a seed), no synchronisation, no copy to the host; the result is bit-repeatable and that of a pair does not
+    depend on the other pairs of the call.  No gradient flows through it."""
+    rp, radius = refine_params(refine), seed_radius(seed)
     if segments is not None:
         N, H, W = _pair(a, b)
         segments = _segment_ids(segments, N, H, W, 0, a.device)
@@ -309,6 +350,10 @@ def dense_flow(a, b, value_range=(0, 1), levels=None, finest=0, iters=12, refine
                 rec = work[rec0:rec0 + N * npy * npx * 3].view(N, npy, npx, 3)
             else:
                 rec, guide = grec[:N * npy * npx * 4].view(N, npy, npx, 4), dict(segments=segments, level=l)
+            if radius is not None and l == n - 1:                     # the seed: match, densify at this level, search from it
+                o = L.c2m_flow_workspace_offset(N, H, W, n, 2, l)     # this level's flow slot; level 0 has none
+                flow = work[o:o + 2 * N * h * w] if l else torch.empty(2 * N * h * w, device=a.device)
+                flow = densify(ia, ib, patch_match(ia, ib, radius, out=rec, **guide), out=flow.view(N, 2, h, w), **guide)
             rec = patch_search(ia, ib, flow, iters, out=rec, **guide)
             if rp is not None:                                        # densify -> refine -> the place the plain flow would go to
                 dense = densify(ia, ib, rec, out=patchflow[:2 * N * h * w].view(N, 2, h, w), **guide)
@@ -360,7 +405,7 @@ def clip_flows(video, num_input_frames, num_predicted_frames, use_fw_of=False, v
     ops.occlusion_splat of the forward chain; with use_fw_of, `target_fw_of` is the forward chain and `target_fw_occ` the map of
     the backward one.  `input_of` / `input_occ` (None for t_in = 1) are the consecutive flows themselves, as compute_flow has
     them, and so is the first target frame.  ONE dense_flow call over the 2 (t_in - 1 + t_out) B consecutive pairs (both
-    directions; dense_flow_kw: levels, finest, iters, refine), two chain launches, the splats and the copies that bring the
+    directions; dense_flow_kw: levels, finest, iters, refine, seed), two chain launches, the splats and the copies that bring the
     results into compute_flow's layout: a number of launches that does not depend on B.
     segments: the int32 ids [B,T,H,W] of every frame of the video: the pair (c_j -> c_j+1) is guided by the ids of frame j, the
     pair (c_j+1 -> c_j) by those of frame j + 1 (dense_flow's `segments`, still ONE call)."""
@@ -401,7 +446,7 @@ class ClassicFlow(nn.Module):
     """dense_flow behind FlowNet's call surface: `flow, conf = ClassicFlow()(A, B)` for 4-D [N,3,H,W], 5-D [b,n,3,H,W] and 6-D
     [b,t,n,3,H,W] inputs, with conf = ops.occlusion_splat(flow)[0] as FlowNet computes it.  value_range defaults to (-1, 1),
     where train.compute_flow puts the frames; ClassicFlow(value_range=(0, 1)).compute_flow_and_conf is the `flow_fn` of
-    interactive.rollout.  refine: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8.
+    interactive.rollout.  refine, seed: as in dense_flow (None: off).  No weights, no resize to multiples of 64: any size >= 8.
     chain=True: train.compute_flow takes its targets from `clip_flows` (the consecutive flows of the clip, chained) instead of
     searching each (last input frame, predicted frame) pair directly; the call surface above is the same either way.
     segments: forward, compute_flow_and_conf and clip_flows take the int32 ids of the first frame of every pair (of every frame
@@ -409,18 +454,20 @@ class ClassicFlow(nn.Module):
 
     takes_segments = True                                             # train.compute_flow asks before it passes `segments`
 
-    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None, chain=False):
+    def __init__(self, value_range=(-1, 1), levels=None, finest=0, iters=12, refine=None, chain=False, seed=None):
         super().__init__()
         self.value_range, self.levels, self.finest, self.iters = tuple(value_range), levels, finest, iters
         refine_params(refine)                                         # a bad parameter raises here, not at the first call
-        self.refine, self.chain = refine, bool(chain)
+        seed_radius(seed)
+        self.refine, self.chain, self.seed = refine, bool(chain), seed
 
     def clip_flows(self, train_batch, train_params, segments=None):
         """train.compute_flow's dict for a batch, by `clip_flows`; the frames go to [-1, 1] first, as compute_flow puts them.
         segments: the int32 ids [B,T,H,W] of every frame."""
         return clip_flows(train_batch["video"] * 2 - 1, train_params["num_input_frames"], train_params["num_predicted_frames"],
                           train_params.get("use_fw_of", False), self.value_range, levels=self.levels, finest=self.finest,
-                          iters=self.iters, refine=self.refine, **({} if segments is None else dict(segments=segments)))
+                          iters=self.iters, refine=self.refine, seed=self.seed,
+                          **({} if segments is None else dict(segments=segments)))
 
     def forward(self, input_A, input_B, segments=None):
         size = input_A.size()
@@ -438,7 +485,7 @@ class ClassicFlow(nn.Module):
         return flow.view(*size[:-3], 2, h, w), conf.view(*size[:-3], 1, h, w)
 
     def compute_flow_and_conf(self, im1, im2, segments=None):
-        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters, self.refine, segments)
+        flow = dense_flow(im1, im2, self.value_range, self.levels, self.finest, self.iters, self.refine, segments, self.seed)
         with torch.no_grad():
             conf = ops.occlusion_splat(flow)[0]
         return flow, conf

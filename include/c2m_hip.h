@@ -457,6 +457,26 @@ int c2m_flow_refine_iterate_guided(const float* flow, long flow_elems, void* wor
                                    float* out, long out_elems, int shift, int Ho, int Wo, const int32_t* segments,
                                    long segment_elems, int level, int H, int W, void* stream);
 
+/* ---- block-matching seed of the coarsest level (dense_flow.hip): c2m_amd.flow.patch_match, dense_flow(seed=...) ---------------
+ * The reference has no counterpart.  On ONE pyramid level, with the patches of c2m_flow_patch_search: ia, ib [N][h][w]
+ * (image_elems floats each) -> records [N][npy][npx][3] = (dx, dy, mean(J) - mean(T)), ONE launch, one wave per patch.  A patch
+ * tries every integer displacement (dx, dy) in [-radius, radius]^2, 1 <= radius <= 8, whose 8 x 8 window lies wholly inside
+ * ib's level (0 <= ox + dx <= w - 8, 0 <= oy + dy <= h - 8; (0, 0) always is; no coordinate is clamped, nothing is interpolated)
+ * and takes the smallest key (cost, dx^2 + dy^2, dy, dx), compared lexicographically.  cost = sum(((J - mJ) - Tm)^2), J ib's
+ * window at the displacement, mJ = sum(J) / 64, both sums over the 64 pixels in raster order (row by row, one term after the
+ * other, from 0); T, mean(T), Tm = T - mean(T) and det are those of the search, and a patch with det <= 40.96 takes (0, 0).
+ * DESIGN.md 4.2q.  The records have the layout of the search's and are densified by c2m_flow_densify.
+ * c2m_flow_patch_match_guided: segments, segment_elems, level, H, W as above; every sum runs over the n >= 1 pixels whose id is
+ *   that of the patch centre, means are sum / n, the threshold is 40.96 * n^2 / 4096, records [N][npy][npx][4] = (.., n).  One
+ *   id everywhere gives the bits of the unguided form.
+ * Every size, extent, alignment and the radius are checked before the launch; N == 0 returns 0; no atomics, no
+ * synchronisation, no host copy: bit-repeatable, and the result of a pair does not depend on N.                                */
+int c2m_flow_patch_match(const float* ia, const float* ib, long image_elems, float* records, long record_elems, int N, int h,
+                         int w, int radius, void* stream);
+int c2m_flow_patch_match_guided(const float* ia, const float* ib, long image_elems, float* records, long record_elems, int N,
+                                int h, int w, int radius, const int32_t* segments, long segment_elems, int level, int H, int W,
+                                void* stream);
+
 /* ---- chains of frame-to-frame flows (flow_chain.hip): c2m_amd.flow.chain_flows, clip_flows ---------------------------------
  * The reference has no counterpart.  Frames c_0 .. c_K of N clips; steps [N][K][2][H][W] fp32, channel 0 = x, pixels, with the
  * convention above; out [N][K][2][H][W]; valid [N][K][H][W] uint8 or NULL.  DESIGN.md 4.2n states the algorithm.
