@@ -777,7 +777,7 @@ def test_losses_golden():
     close(ssim, o["ssim"], 1e-5, 1e-6, "ssim")
     close(l1, o["l1"], 1e-5, 1e-6, "l1")
     close(l1m, o["l1_masked"], 1e-5, 1e-6, "masked l1")
-    close(a.grad, gin["a"], 1e-3, 1e-7, "d a")
+    close(a.grad, gin["a"], 1e-5, 1e-8, "d a")      # max|d a| is 2.1e-3; test_gpu_loss_edges.py: both sides within 1e-6 of it
 
 
 def test_l1_mean_grad_to_second_argument():
