@@ -27,6 +27,7 @@ SOURCES = {"conv_igemm.hip": NOSLP, "conv_gather.hip": NOSLP, "conv_patch.hip": 
            "flow_chain.hip": ["-ffp-contract=off"] + NOSLP,
            "detail_warp.hip": ["-ffp-contract=off"] + NOSLP,
            "quality.hip": ["-ffp-contract=off"] + NOSLP,
+           "flow_score.hip": ["-ffp-contract=off"] + NOSLP,
            "instance_link.hip": ["-ffp-contract=off"] + NOSLP,
            "panoptic.hip": ["-ffp-contract=off"] + NOSLP,
            "components.hip": NOSLP,                      # integer kernels: nothing to contract

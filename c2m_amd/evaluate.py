@@ -6,13 +6,15 @@ tracker says it should be.  FID and FVD are not provided (they need Inception / 
 
 Differences from the reference, all documented in DESIGN §4.2f: the detector runs ONCE on the 2B frames instead of once per
 object; candidates with equal scores keep their box order; a non-finite head box is removed instead of looping for ever."""
+import ctypes
+import math
 import statistics
 import warnings
 
 import numpy as np
 import torch
 
-from . import ops, segment
+from . import _lib, ops, segment
 from .modules.networks.yolo_v3 import Darknet
 
 _GRAPH_FIELDS = ("target_frames_nodes_roi", "x", "batch")
@@ -450,3 +452,409 @@ class MapScore:
                 f.write(f"class {c} pq {g['pq']} sq {g['sq']} rq {g['rq']}\n")
             f.write("\n\n")
         return r
+
+
+# ------------------------------------------------------------------------------------------ flow scores: endpoint error and consistency
+# What optical-flow work reports (Sintel's EPE and speed buckets, KITTI's Fl, Barron's angular error) and, for clips without
+# ground truth, what the flows say about themselves: the photometric error of the warp and the forward-backward distance
+# (csrc/flow_score.hip).  Flows are in pixels, channel 0 = x, a(x) ~ b(x + flow(x)).
+FLOW_REGIONS = ("object", "background", "boundary", "occluded", "slow", "medium", "fast")
+FLOW_QUALITY_COLUMNS = ("n", "n_nonfinite", "sum_epe", "sum_e2", "sum_mag", "sum_ae", "n_out", "n_gt1", "n_gt3", "n_gt5")
+FLOW_CONSISTENCY_COLUMNS = ("n", "n_inside", "sum_photo", "sum_photo2", "sum_fb", "n_incons", "sum_photo_cons")
+FLOW_SCORE_ROWS = 9         # every counted pixel, then region bits 0..7
+_FLOW_FLOATS = (torch.float32, torch.bfloat16)
+
+
+def _flow_operand(name, x, channels, dtypes):
+    """Type, dtype, rank and channel checks of one [N,C,H,W] / [B,C,T,H,W] operand -> (B, T, H, W, lead) with lead (N,) or (B, T)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"{name} must be [N,C,H,W] or [B,C,T,H,W], got {tuple(x.shape)}")
+    if x.shape[1] not in channels:
+        raise ValueError(f"{name} must have {' or '.join(str(c) for c in channels)} channels, got {x.shape[1]} in {tuple(x.shape)}")
+    if x.dim() == 4:
+        (N, _, H, W), T, lead = x.shape, 1, (x.shape[0],)
+    else:
+        (N, _, T, H, W), lead = x.shape, (x.shape[0], x.shape[2])
+    if H < 1 or W < 1:
+        raise ValueError(f"{name} must hold at least one pixel, got {tuple(x.shape)}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"one {H}x{W} frame has 2^31 pixels or more")
+    return N, T, H, W, lead
+
+
+def _flow_same(name, x, ref_name, ref):
+    if x.dim() != ref.dim() or x.shape[0] != ref.shape[0] or x.shape[2:] != ref.shape[2:]:
+        raise ValueError(f"{name} {tuple(x.shape)} and {ref_name} {tuple(ref.shape)} differ in rank, pairs or size")
+
+
+def _flow_mask(name, m, lead, H, W, like):
+    """A uint8 per-pixel operand (valid, regions): lead + (H, W), on the device of `like`."""
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor):
+        raise TypeError(f"{name} must be a uint8 tensor or None, got {type(m).__name__}")
+    if m.dtype != torch.uint8:
+        raise TypeError(f"{name} must be uint8, got {m.dtype}")
+    if tuple(m.shape) != tuple(lead) + (H, W):
+        raise ValueError(f"{name} must be {tuple(lead) + (H, W)}, got {tuple(m.shape)}")
+    if m.device != like.device:
+        raise ValueError(f"{name} must be on the device of the flows ({like.device}), got {m.device}")
+    return m
+
+
+def _flow_planes(x):
+    """x with dense H x W planes and distinct channels (a copy only if they are not) and its (B, C, T) strides in elements.  A
+    B- or T-strided or expanded view (flows[:, :, 1:], one frame repeated along T) goes in as it is."""
+    x = x.detach()
+    H, W = x.shape[-2:]
+    dense = (W == 1 or x.stride(-1) == 1) and (H == 1 or x.stride(-2) == W) and (x.shape[1] == 1 or x.stride(1) >= H * W)
+    if not dense:
+        x = x.contiguous()
+    s = x.stride()
+    return x, ((s[0], s[1], s[2]) if x.dim() == 5 else (s[0], s[1], 0))
+
+
+def _same_device(pairs, first):
+    for name, t in pairs:
+        if t is not None and t.device != first.device:
+            raise ValueError(f"{name} must be on the device of the first operand ({first.device}), got {t.device}")
+
+
+def flow_quality_sums(pred, target, valid=None, regions=None):
+    """The error sums of the flow `pred` against `target` (csrc/flow_score.hip): float64 [N,9,10] (or [B,T,9,10]) on the device,
+    row 0 the scored pixels, row 1 + k those whose `regions` byte has bit k, columns FLOW_QUALITY_COLUMNS.
+
+    pred fp32 or bf16, target fp32: [N,2,H,W] or [B,2,T,H,W]; B-, T- and channel-strided views go in without a copy.  valid,
+    regions: uint8 [N,H,W] / [B,T,H,W] or None.  A pixel is scored when valid != 0 and both target components are finite and
+    below 1e9 in magnitude (KITTI's sparse ground truth, Sintel's invalid marker); a scored pixel whose pred is not finite adds
+    nothing to the sums and counts in n, n_nonfinite and all four threshold counts.  All arithmetic fp64; two launches, no
+    atomics, bit-repeatable, nothing read back, no autograd."""
+    B, T, H, W, lead = _flow_operand("pred", pred, (2,), _FLOW_FLOATS)
+    _flow_operand("target", target, (2,), (torch.float32,))
+    _flow_same("target", target, "pred", pred)
+    valid = _flow_mask("valid", valid, lead, H, W, pred)
+    regions = _flow_mask("regions", regions, lead, H, W, pred)
+    _same_device((("target", target),), pred)
+    ops._hip_only(pred, target, valid, regions)
+    ops._on_current_device(pred, target, valid, regions)
+    pred, sp = _flow_planes(pred)
+    target, st = _flow_planes(target)
+    valid, regions = (None if m is None else m.contiguous() for m in (valid, regions))
+    out = torch.zeros(*lead, FLOW_SCORE_ROWS, len(FLOW_QUALITY_COLUMNS), device=pred.device, dtype=torch.float64)
+    if B * T:
+        L = _lib.lib()
+        nbytes = L.c2m_flow_quality_workspace_bytes(B, T, H, W)
+        work = torch.empty(nbytes // 8, device=pred.device, dtype=torch.float64)
+        _lib.check(L.c2m_flow_quality(ops._p(pred), ops._p(target), ops._p(valid), ops._p(regions), ops._dt(pred), B, T, H, W,
+                                      (ctypes.c_long * 3)(*sp), (ctypes.c_long * 3)(*st), ops._p(work), nbytes, ops._p(out),
+                                      ops._stream()), "flow_quality")
+    return out
+
+
+def flow_consistency_sums(flow_ab, a, b, flow_ba=None, regions=None, alpha1=0.01, alpha2=0.5, maps=False):
+    """The ground-truth-free check of the flow a -> b (csrc/flow_score.hip): float64 [N,9,7] (or [B,T,9,7]) on the device, row 0
+    every pixel of a, row 1 + k those whose `regions` byte has bit k, columns FLOW_CONSISTENCY_COLUMNS.
+
+    flow_ab, flow_ba (the flow b -> a, or None): fp32 [N,2,H,W] or [B,2,T,H,W]; a, b: fp32 or bf16 with 1 or 3 channels, any value
+    range, finite; strided views go in without a copy (a frame repeated along T too).  A pixel x is inside when its flow is finite
+    and y = x + flow_ab(x) lies in the frame; there b and flow_ba are sampled bilinearly at y in fp64: photo = mean over channels
+    of |a(x) - b(y)|, fb = |flow_ab(x) + flow_ba(y)|, and the pixel is inconsistent when fb^2 > alpha1 (|flow_ab(x)|^2 +
+    |flow_ba(y)|^2) + alpha2 (UnFlow's occlusion test; a non-finite flow_ba(y) is inconsistent and adds nothing to sum_fb).
+    Without flow_ba the last three columns are NaN.
+    maps=True: returns (sums, {"photo", "fb": fp32 [N,H,W] / [B,T,H,W], NaN outside; "inconsistent": uint8}), written by the same
+    launch.  Two launches, no atomics, bit-repeatable, nothing read back, no autograd."""
+    for name, al in (("alpha1", alpha1), ("alpha2", alpha2)):
+        if isinstance(al, bool) or not isinstance(al, (int, float)):
+            raise TypeError(f"{name} must be a number, got {type(al).__name__}")
+        if not math.isfinite(al) or al < 0:
+            raise ValueError(f"{name} must be finite and >= 0, got {al}")
+    B, T, H, W, lead = _flow_operand("flow_ab", flow_ab, (2,), (torch.float32,))
+    _flow_operand("a", a, (1, 3), _FLOW_FLOATS)
+    _flow_operand("b", b, (1, 3), _FLOW_FLOATS)
+    _flow_same("a", a, "flow_ab", flow_ab)
+    _flow_same("b", b, "flow_ab", flow_ab)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"a has {a.shape[1]} channels and b {b.shape[1]}")
+    if flow_ba is not None:
+        _flow_operand("flow_ba", flow_ba, (2,), (torch.float32,))
+        _flow_same("flow_ba", flow_ba, "flow_ab", flow_ab)
+    regions = _flow_mask("regions", regions, lead, H, W, flow_ab)
+    _same_device((("a", a), ("b", b), ("flow_ba", flow_ba)), flow_ab)
+    ops._hip_only(flow_ab, a, b, flow_ba, regions)
+    ops._on_current_device(flow_ab, a, b, flow_ba, regions)
+    if a.dtype != b.dtype:                               # fp32 against bf16: bf16 -> fp32 is exact
+        a, b = a.float(), b.float()
+    C = a.shape[1]
+    strides = []
+    flow_ab, s = _flow_planes(flow_ab)
+    strides += s
+    a, s = _flow_planes(a)
+    strides += s
+    b, s = _flow_planes(b)
+    strides += s
+    if flow_ba is not None:
+        flow_ba, s = _flow_planes(flow_ba)
+        strides += s
+    else:
+        strides += (0, 0, 0)
+    regions = None if regions is None else regions.contiguous()
+    dev = flow_ab.device
+    out = torch.zeros(*lead, FLOW_SCORE_ROWS, len(FLOW_CONSISTENCY_COLUMNS), device=dev, dtype=torch.float64)
+    if flow_ba is None:
+        out[..., 4:] = _NAN
+    m = None
+    if maps:
+        m = {"photo": torch.full((*lead, H, W), _NAN, device=dev, dtype=torch.float32),
+             "fb": torch.full((*lead, H, W), _NAN, device=dev, dtype=torch.float32),
+             "inconsistent": torch.zeros(*lead, H, W, device=dev, dtype=torch.uint8)}
+    if B * T:
+        L = _lib.lib()
+        nbytes = L.c2m_flow_consistency_workspace_bytes(B, T, H, W)
+        work = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+        mp = (None, None, None) if m is None else (ops._p(m["photo"]), ops._p(m["fb"]), ops._p(m["inconsistent"]))
+        _lib.check(L.c2m_flow_consistency(ops._p(flow_ab), ops._p(a), ops._p(b), ops._p(flow_ba), ops._p(regions), ops._dt(a),
+                                          B, C, T, H, W, (ctypes.c_long * 12)(*strides), float(alpha1), float(alpha2), *mp,
+                                          ops._p(work), nbytes, ops._p(out), ops._stream()), "flow_consistency")
+    return (out, m) if maps else out
+
+
+def _region_count(region_names):
+    k = 8 if region_names is None else len(region_names)
+    if not 0 <= k <= 8:
+        raise ValueError("a region byte has 8 bits")
+    return k
+
+
+def _split_rows(values, k):
+    out = {}
+    for key, v in values.items():
+        out[key] = v[..., 0]
+        out["region_" + key] = v[..., 1:1 + k]
+    return out
+
+
+def flow_quality_from_sums(sums, region_names=None):
+    """The host arithmetic of flow_quality: sums [...,9,10] float64 (FLOW_QUALITY_COLUMNS) -> the result dict.  The means of the
+    error sums are over the scored pixels with a finite pred (n - n_nonfinite), the rates over all scored pixels (n)."""
+    sums = torch.as_tensor(sums, dtype=torch.float64)
+    if sums.dim() < 2 or tuple(sums.shape[-2:]) != (FLOW_SCORE_ROWS, len(FLOW_QUALITY_COLUMNS)):
+        raise ValueError(f"sums must be [...,{FLOW_SCORE_ROWS},{len(FLOW_QUALITY_COLUMNS)}], got {tuple(sums.shape)}")
+    n, bad, s_epe, s_e2, s_mag, s_ae, n_out, g1, g3, g5 = sums.unbind(-1)
+    fin = n - bad
+    v = {"epe": _div(s_epe, fin), "rmse": torch.sqrt(_div(s_e2, fin)), "ae_deg": _div(s_ae, fin) * (180.0 / math.pi),
+         "magnitude": _div(s_mag, fin), "fl": _div(n_out, n), "bad1": _div(g1, n), "bad3": _div(g3, n), "bad5": _div(g5, n),
+         "nonfinite": bad, "pixels": n}
+    return _split_rows(v, _region_count(region_names))
+
+
+def flow_consistency_from_sums(sums, region_names=None):
+    """The host arithmetic of flow_consistency: sums [...,9,7] float64 (FLOW_CONSISTENCY_COLUMNS) -> the result dict: photo,
+    photo_rms and fb are means over the inside pixels, photo_consistent over the inside pixels that pass the forward-backward
+    test, inconsistent the share of the inside pixels that fail it, outside the share of all pixels whose target leaves the frame."""
+    sums = torch.as_tensor(sums, dtype=torch.float64)
+    if sums.dim() < 2 or tuple(sums.shape[-2:]) != (FLOW_SCORE_ROWS, len(FLOW_CONSISTENCY_COLUMNS)):
+        raise ValueError(f"sums must be [...,{FLOW_SCORE_ROWS},{len(FLOW_CONSISTENCY_COLUMNS)}], got {tuple(sums.shape)}")
+    n, n_in, s_p, s_p2, s_fb, n_inc, s_pc = sums.unbind(-1)
+    v = {"photo": _div(s_p, n_in), "photo_rms": torch.sqrt(_div(s_p2, n_in)), "photo_consistent": _div(s_pc, n_in - n_inc),
+         "fb": _div(s_fb, n_in), "inconsistent": _div(n_inc, n_in), "outside": _div(n - n_in, n), "pixels": n}
+    return _split_rows(v, _region_count(region_names))
+
+
+def flow_quality(pred, target, valid=None, regions=None, region_names=None):
+    """Endpoint error, angular error and outlier rates of the flow `pred` against `target` (flow_quality_sums), on the host after
+    one copy.  Returns float64 tensors [N] (or [B,T]): epe (px), rmse (px), ae_deg (Barron's angular error, degrees), magnitude
+    (mean |target|), fl (KITTI: error > 3 px and > 5 % of |target|), bad1, bad3, bad5 (error > 1, 3, 5 px), nonfinite, pixels;
+    region_* [...,8] (or len(region_names)); "sums", the raw sums (what FlowScore.update takes).  NaN where a region holds no
+    scored pixel."""
+    sums = flow_quality_sums(pred, target, valid, regions).cpu()                   # the one copy to the host
+    return dict(flow_quality_from_sums(sums, region_names), sums=sums)
+
+
+def flow_consistency(flow_ab, a, b, flow_ba=None, regions=None, region_names=None, alpha1=0.01, alpha2=0.5, maps=False):
+    """The ground-truth-free score of the flow a -> b (flow_consistency_sums), on the host after one copy.  Returns float64
+    tensors [N] (or [B,T]): photo, photo_rms, photo_consistent, fb (px), inconsistent, outside, pixels; region_*; "sums"; with
+    maps=True also the device maps photo_map, fb_map (fp32, NaN outside) and inconsistent_map (uint8).  fb, inconsistent and
+    photo_consistent are NaN without flow_ba.
+    What it cannot see: a textureless region has a low photometric error for any flow, and the forward-backward test flags a
+    disocclusion as an error by design."""
+    r = flow_consistency_sums(flow_ab, a, b, flow_ba, regions, alpha1, alpha2, maps)
+    sums = (r[0] if maps else r).cpu()                                              # the one copy to the host
+    out = dict(flow_consistency_from_sums(sums, region_names), sums=sums)
+    if maps:
+        out.update({k + "_map": v for k, v in r[1].items()})
+    return out
+
+
+def flow_regions(target, instance=None, occlusion=None, occ_threshold=0.5, band=4, jump=1.0, speeds=(10.0, 40.0),
+                 id_range=(1000, 19000)):
+    """The region bytes of flow_quality / flow_consistency for target flows [N,2,H,W] or [B,2,T,H,W] -> uint8 [N,H,W] / [B,T,H,W]
+    on the target's device, bits in the order of FLOW_REGIONS:
+    object: `instance` ([N,H,W] / [B,T,H,W], or with a channel axis of 1) holds an id with id_range[0] <= id < id_range[1];
+    background: every other pixel (all of them without `instance`);
+    boundary: within `band` px (Chebyshev) of a pixel whose target flow differs from a 4-neighbour's by more than `jump` px or,
+    with `instance`, whose id differs from a 4-neighbour's;
+    occluded: `occlusion` (same shapes) is below occ_threshold;
+    slow / medium / fast: |target| < speeds[0], < speeds[1], >= speeds[1] (Sintel's s0-10, s10-40, s40+), decided on squares in
+    float64.  Plain torch on the device."""
+    if not isinstance(target, torch.Tensor) or target.dim() not in (4, 5) or target.shape[1] != 2:
+        raise ValueError("target must be [N,2,H,W] or [B,2,T,H,W]")
+    if not isinstance(band, int) or isinstance(band, bool) or band < 0:
+        raise ValueError(f"band must be an int >= 0, got {band!r}")
+    s0, s1 = (float(s) for s in speeds)
+    if not (0.0 <= s0 <= s1 and math.isfinite(s1)) or not (math.isfinite(jump) and jump >= 0):
+        raise ValueError(f"speeds must be two finite, ordered, non-negative values and jump finite and >= 0, got {speeds}, {jump}")
+    lo, hi = (int(v) for v in id_range)
+    t = target.detach().double()
+    u, v = t[:, 0], t[:, 1]                                                        # [N,H,W] or [B,T,H,W]
+    lead, (H, W) = tuple(u.shape[:-2]), u.shape[-2:]
+
+    def plane(name, x):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+        if x.dim() == u.dim() + 1 and x.shape[1] == 1:
+            x = x[:, 0]
+        if tuple(x.shape) != tuple(u.shape):
+            raise ValueError(f"{name} must be {tuple(u.shape)} (or with a channel axis of 1), got {tuple(x.shape)}")
+        if x.device != target.device:
+            raise ValueError(f"{name} must be on the device of target ({target.device}), got {x.device}")
+        return x
+
+    def neighbours(differs):
+        """differs(p, q) on the two slices of each 4-neighbour pair -> the pixels on either side of a differing pair."""
+        e = torch.zeros(u.shape, dtype=torch.bool, device=u.device)
+        dx = differs(lambda x: x[..., :, 1:], lambda x: x[..., :, :-1])
+        e[..., :, 1:] |= dx
+        e[..., :, :-1] |= dx
+        dy = differs(lambda x: x[..., 1:, :], lambda x: x[..., :-1, :])
+        e[..., 1:, :] |= dy
+        e[..., :-1, :] |= dy
+        return e
+
+    edge = neighbours(lambda p, q: (p(u) - q(u)) * (p(u) - q(u)) + (p(v) - q(v)) * (p(v) - q(v)) > float(jump) * float(jump))
+    bits = torch.zeros(u.shape, dtype=torch.uint8, device=u.device)
+    if instance is not None:
+        inst = plane("instance", instance)
+        obj = (inst >= lo) & (inst < hi)
+        edge |= neighbours(lambda p, q: p(inst) != q(inst))
+    else:
+        obj = torch.zeros(u.shape, dtype=torch.bool, device=u.device)
+    bits += obj.to(torch.uint8) + (~obj).to(torch.uint8) * 2
+    if band > 0:
+        e = edge.reshape(-1, 1, H, W).to(torch.float32)
+        edge = (torch.nn.functional.max_pool2d(e, 2 * band + 1, 1, band) > 0).reshape(u.shape)
+    bits += edge.to(torch.uint8) * 4
+    if occlusion is not None:
+        bits += (plane("occlusion", occlusion) < occ_threshold).to(torch.uint8) * 8
+    m2 = u * u + v * v
+    bits += (m2 < s0 * s0).to(torch.uint8) * 16 + ((m2 >= s0 * s0) & (m2 < s1 * s1)).to(torch.uint8) * 32 + \
+        (m2 >= s1 * s1).to(torch.uint8) * 64
+    return bits.contiguous()
+
+
+class FlowScore:
+    """Flow scores over a dataset, shaped like QualityScore.  kind "quality" takes flow_quality results (or their raw sums),
+    kind "consistency" flow_consistency results.  Every quantity is reported twice: `<key>` is the pixel-weighted figure over
+    everything seen -- the sums of all pairs added, then the host arithmetic: Sintel's EPE, KITTI's Fl-all -- and `<key>_mean`
+    the mean over pairs of the per-pair values (NaN entries, pairs with an empty region, left out); both overall and, as
+    `_per_frame` lists, per frame index, for the whole frame and as `<region>_<key>` per region.  Sums with an [N] lead count as
+    one frame index."""
+    _KINDS = {"quality": (FLOW_QUALITY_COLUMNS, flow_quality_from_sums,
+                          ("epe", "rmse", "ae_deg", "fl", "bad1", "bad3", "bad5", "nonfinite", "pixels")),
+              "consistency": (FLOW_CONSISTENCY_COLUMNS, flow_consistency_from_sums,
+                              ("photo", "photo_consistent", "fb", "inconsistent", "outside", "pixels"))}
+
+    def __init__(self, kind="quality", region_names=FLOW_REGIONS):
+        if kind not in self._KINDS:
+            raise ValueError(f"kind must be one of {sorted(self._KINDS)}, got {kind!r}")
+        self.kind, self.region_names = kind, tuple(region_names)
+        _region_count(self.region_names)
+        self.columns, self.from_sums, self.keys = self._KINDS[kind]
+        self.rows = []                                   # each entry [B,T,9,K]
+
+    def update(self, result):
+        sums = result["sums"] if isinstance(result, dict) else result
+        sums = torch.as_tensor(sums.cpu() if isinstance(sums, torch.Tensor) else sums, dtype=torch.float64)
+        if sums.dim() not in (3, 4) or tuple(sums.shape[-2:]) != (FLOW_SCORE_ROWS, len(self.columns)):
+            raise ValueError(f"a {self.kind} score takes sums [N,{FLOW_SCORE_ROWS},{len(self.columns)}] or [B,T,..], got "
+                             f"{tuple(sums.shape)}")
+        if sums.dim() == 3:
+            sums = sums.unsqueeze(1)
+        if self.rows and sums.shape[1] != self.rows[0].shape[1]:
+            raise ValueError("results with different numbers of frames")
+        self.rows.append(sums)
+
+    def _flat(self, sums):
+        """from_sums -> {key: [..., 1 + R]}: the frame, then the regions."""
+        r = self.from_sums(sums, self.region_names)
+        return {k: torch.cat([r[k].unsqueeze(-1), r["region_" + k]], -1) for k in self.keys}
+
+    def result(self):
+        names = ("frame",) + self.region_names
+        K = len(self.columns)
+        v = torch.cat(self.rows, 0) if self.rows else torch.zeros(0, 0, FLOW_SCORE_ROWS, K, dtype=torch.float64)
+        pooled, pooled_t, each = self._flat(v.sum((0, 1))), self._flat(v.sum(0)), self._flat(v)
+        out = {}
+        for k in self.keys:
+            mean, mean_t = QualityScore._mean(each[k], (0, 1)), QualityScore._mean(each[k], 0)
+            for i, name in enumerate(names):
+                key = k if i == 0 else f"{name}_{k}"
+                out[key] = float(pooled[k][i])
+                out[key + "_per_frame"] = pooled_t[k][:, i].tolist()
+                out[key + "_mean"] = float(mean[i])
+                out[key + "_mean_per_frame"] = mean_t[:, i].tolist()
+        out["pairs"] = int(v.shape[0] * v.shape[1])
+        return out
+
+    def write(self, path):
+        r = self.result()
+        with open(path, "a") as f:
+            f.write(f"{self.kind} pairs {r['pairs']}\n")
+            for name in ("",) + tuple(n + "_" for n in self.region_names):
+                for k in self.keys:
+                    f.write(f"{name}{k} {r[name + k]} {name}{k}_mean {r[name + k + '_mean']}\n")
+                    f.write(f"{name}{k}_per_frame {' '.join(str(x) for x in r[name + k + '_per_frame'])}\n")
+                    f.write(f"{name}{k}_mean_per_frame {' '.join(str(x) for x in r[name + k + '_mean_per_frame'])}\n")
+            f.write("\n\n")
+        return r
+
+
+def clip_flow_check(video, flows, num_input_frames, regions=None, region_names=None, alpha1=0.01, alpha2=0.5, maps=False):
+    """Scores what train.compute_flow returned for a batch, without ground truth: video [B,C,T,H,W] (fp32 or bf16, C 1 or 3),
+    flows the dict of compute_flow, num_input_frames = t_in.  Returns {"target_bw": ..., "target_fw": ..., "input": ...}, each
+    a flow_consistency result with [B, frames] entries, for the entries the dict holds:
+    target_bw_of[:, :, i]: a = frame t_in + i, b = frame t_in - 1, with target_fw_of as the reverse flow when it is there;
+    target_fw_of[:, :, i]: a = frame t_in - 1, b = frame t_in + i, with target_bw_of as the reverse flow;
+    input_of[:, :, i]: a = frame i, b = frame i + 1; no reverse flow is in the dict, so its forward-backward figures are NaN.
+    The photometric figures are always given.  regions: None or a dict with the same keys of uint8 [B,frames,H,W] region bytes.
+    No frame is copied: the pairs are strided views of the video.  This is how ClassicFlow() is compared with
+    ClassicFlow(seed=True, refine=True, chain=True) on one's own clips: lower photo and fb on the same clip is the better flow.
+
+    For pixel-unit flow targets only (a(x) ~ b(x + flow(x))).  The generator's dense_motion_bw follows ops.flow_warp's grid
+    convention: score it with flow_quality against target_bw_of, not with this call."""
+    if not isinstance(video, torch.Tensor) or video.dim() != 5:
+        raise ValueError("video must be [B,C,T,H,W]")
+    if not isinstance(flows, dict) or not isinstance(flows.get("target_bw_of"), torch.Tensor):
+        raise ValueError("flows must be the dict of train.compute_flow (it holds target_bw_of)")
+    t_in = int(num_input_frames)
+    bw, fw, inp = flows["target_bw_of"], flows.get("target_fw_of"), flows.get("input_of")
+    if bw.dim() != 5:
+        raise ValueError(f"target_bw_of must be [B,2,T,H,W], got {tuple(bw.shape)}")
+    t_out = bw.shape[2]
+    if t_in < 1 or video.shape[2] < t_in + t_out:
+        raise ValueError(f"video holds {video.shape[2]} frames; {t_in} input frames and {t_out} flow targets need {t_in + t_out}")
+    if regions is not None and not isinstance(regions, dict):
+        raise TypeError("regions must be None or a dict with the keys of the result")
+    reg = regions or {}
+    future = video[:, :, t_in:t_in + t_out]
+    last = video[:, :, t_in - 1:t_in].expand(-1, -1, t_out, -1, -1)
+    kw = dict(region_names=region_names, alpha1=alpha1, alpha2=alpha2, maps=maps)
+    out = {"target_bw": flow_consistency(bw, future, last, fw, reg.get("target_bw"), **kw)}
+    if fw is not None:
+        out["target_fw"] = flow_consistency(fw, last, future, bw, reg.get("target_fw"), **kw)
+    if inp is not None and t_in > 1:
+        out["input"] = flow_consistency(inp, video[:, :, :t_in - 1], video[:, :, 1:t_in], None, reg.get("input"), **kw)
+    return out

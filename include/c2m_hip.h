@@ -523,6 +523,35 @@ int c2m_frame_quality(const void* pred, const void* target, const uint8_t* regio
                       const long* pred_strides, const long* target_strides, const double* weights, double L, void* workspace,
                       long workspace_bytes, double* out, void* stream);
 
+/* ---- flow scores (flow_score.hip): c2m_amd.evaluate.flow_quality, flow_consistency -------------------------------------------
+ * The reference has no counterpart.  Flows in pixels, channel 0 = x, a(x) ~ b(x + flow(x)).  B*T pairs, H, W >= 1, H * W < 2^31.
+ * Every operand is one or two or C planes of H * W dense elements per pair; its HOST stride triple (B, C, T), in elements,
+ * places plane c of pair (b, t) at b * sB + c * sC + t * sT (none negative, sC >= H * W; a zero sB or sT repeats a frame).
+ * valid, regions [B][T][H][W] uint8, dense, or NULL.  out [B][T][9][K] float64: row 0 every counted pixel, row 1 + k those whose
+ * regions byte has bit k (zero when regions is NULL).  All per-pixel arithmetic is fp64 on exactly converted inputs, in the
+ * operation order written at the top of flow_score.hip and in DESIGN.md 4.2r; thresholds compare squared quantities.
+ * c2m_flow_quality: pred fp32 (pred_dt 0) or bf16 (1), target fp32, both [..][2][..].  K = 10: (n, n_nonfinite, sum_epe, sum_e2,
+ *   sum_mag, sum_ae, n_out, n_gt1, n_gt3, n_gt5).  A pixel is scored when valid != 0 and both target components are finite and
+ *   below 1e9 in magnitude; a scored pixel with a non-finite pred component adds nothing to the sums and counts in n,
+ *   n_nonfinite and all four threshold counts.
+ * c2m_flow_consistency: flow_ab, flow_ba (or NULL) fp32 [..][2][..], a, b fp32 (image_dt 0) or bf16 (1) with C = 1 or 3 planes;
+ *   strides: HOST array of the four triples of flow_ab, a, b, flow_ba (the last unused when flow_ba is NULL).  K = 7: (n, n_inside,
+ *   sum_photo, sum_photo2, sum_fb, n_incons, sum_photo_cons), the last three NaN when flow_ba is NULL.  alpha1, alpha2 finite and
+ *   >= 0.  photo, fb (fp32) and inconsistent (uint8), each [B][T][H][W] dense, all three or all NULL: per-pixel maps written by
+ *   the same launch (photo, fb NaN outside the frame).
+ * workspace: the matching *_workspace_bytes(B, T, H, W) bytes.  Two launches each (1024-pixel tiles, then one workgroup per
+ * pair adds the tiles' partials in a fixed order); no atomics, no synchronisation, no host copy: bit-repeatable, and the sums
+ * of a pair do not depend on B or T.  B * T == 0 returns 0.                                                                     */
+long c2m_flow_quality_workspace_bytes(int B, int T, int H, int W);
+int c2m_flow_quality(const void* pred, const float* target, const uint8_t* valid, const uint8_t* regions, int pred_dt, int B,
+                     int T, int H, int W, const long* pred_strides, const long* target_strides, void* workspace,
+                     long workspace_bytes, double* out, void* stream);
+long c2m_flow_consistency_workspace_bytes(int B, int T, int H, int W);
+int c2m_flow_consistency(const float* flow_ab, const void* a, const void* b, const float* flow_ba, const uint8_t* regions,
+                         int image_dt, int B, int C, int T, int H, int W, const long* strides, double alpha1, double alpha2,
+                         float* photo, float* fb, uint8_t* inconsistent, void* workspace, long workspace_bytes, double* out,
+                         void* stream);
+
 /* ---- loss reductions (losses.hip) ---------------------------------------------------------------------------
  * losses/losses.py:180-189 L1MaskedLoss (also :60-65 VGG L1, model.py:118-121 feature matching); :152-177 SSIM. */
 int c2m_l1_mean_fwd(const void* a, const void* b, const float* mask, float* out, long total, int C, long inner,
