@@ -240,3 +240,80 @@ C2M_API int c2m_instance_match(const int32_t* pairs, const int32_t* ref_slots, c
                        frame_slots, frame_count, link, max_nodes, iou_num, iou_den, same_class);
     return (int)hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------ relabel
+// A plane's ids rewritten through its (from, to) list: c2m_amd.tracking.anchor_maps puts the maps of the real frames into the
+// id space of the anchor with it.  The list (at most 64 pairs, from ascending) sits in LDS and a pixel's pair is found by the
+// binary search of slot_of, so the mapping is simultaneous -- a pixel is looked up by its OLD value only, and two ids may swap.
+// A thread reuses the result of the pixel before it when the value repeats.  Integer code only.
+#define C2M_RELABEL_VEC 4
+#define C2M_RELABEL_ROUNDS 8
+#define C2M_RELABEL_STRIP (256 * C2M_RELABEL_VEC * C2M_RELABEL_ROUNDS)    // pixels per workgroup
+
+struct RelabelP {
+    const int* maps; int* out;                              // [P][HW]
+    const int* from; const int* to; const int* count;       // [P][64], [P][64], [P]
+    const uint8_t* thing;                                   // [256]
+    long HW; int strips, divisor;
+};
+
+__device__ __forceinline__ int relabel_value(const int* s_from, const int* s_to, int n, int v, int divisor, const uint8_t* thing) {
+    const int pos = slot_of(s_from, n, v, -1);
+    if (pos >= 0) return s_to[pos];
+    if (v >= divisor) {
+        const int cat = v / divisor;
+        if (cat < 256 && thing[cat]) return cat * divisor;                // an unlinked object: its class's crowd id
+    }
+    return v;
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void instance_relabel_kernel(const RelabelP p) {
+    __shared__ int s_from[C2M_LINK_MAX_NODES], s_to[C2M_LINK_MAX_NODES];
+    __shared__ uint8_t s_thing[256];
+    const int tid = threadIdx.x;
+    const int plane = blockIdx.x / p.strips, strip = blockIdx.x - plane * p.strips;
+    const int n = min(max(p.count[plane], 0), C2M_LINK_MAX_NODES);
+    if (tid < C2M_LINK_MAX_NODES) {
+        s_from[tid] = tid < n ? p.from[(long)plane * C2M_LINK_MAX_NODES + tid] : 0x7fffffff;
+        s_to[tid] = tid < n ? p.to[(long)plane * C2M_LINK_MAX_NODES + tid] : 0;
+    }
+    s_thing[tid] = p.thing[tid];
+    __syncthreads();
+    const int* __restrict__ in = p.maps + plane * p.HW;
+    int* __restrict__ out = p.out + plane * p.HW;
+    const long q0 = (long)strip * (256 * VEC * C2M_RELABEL_ROUNDS);
+#pragma unroll 2
+    for (int r = 0; r < C2M_RELABEL_ROUNDS; ++r) {
+        const long q = q0 + ((long)r * 256 + tid) * VEC;
+        if (q >= p.HW) break;                                             // VEC = 4 only when HW % 4 == 0: q + 3 < HW as well
+        if constexpr (VEC == 4) {
+            const int4 a = *reinterpret_cast<const int4*>(in + q);
+            int4 o;
+            o.x = relabel_value(s_from, s_to, n, a.x, p.divisor, s_thing);
+            o.y = a.y == a.x ? o.x : relabel_value(s_from, s_to, n, a.y, p.divisor, s_thing);
+            o.z = a.z == a.y ? o.y : relabel_value(s_from, s_to, n, a.z, p.divisor, s_thing);
+            o.w = a.w == a.z ? o.z : relabel_value(s_from, s_to, n, a.w, p.divisor, s_thing);
+            *reinterpret_cast<int4*>(out + q) = o;
+        } else {
+            out[q] = relabel_value(s_from, s_to, n, in[q], p.divisor, s_thing);
+        }
+    }
+}
+
+C2M_API int c2m_instance_relabel(const int32_t* maps, int32_t* out, const int32_t* from, const int32_t* to, const int32_t* count,
+                                 const uint8_t* thing_table, int P, long HW, int label_divisor, void* stream) {
+    C2M_ENTER();
+    if (P < 0 || HW < 0 || HW >= (1L << 31) || label_divisor < 1) return (int)hipErrorInvalidValue;
+    if (P == 0 || HW == 0) return 0;
+    if (!maps || !out || !from || !to || !count || !thing_table || maps == out) return (int)hipErrorInvalidValue;
+    const bool vec = HW % 4 == 0 && c2m_aligned(16, maps, out);           // plane bases are multiples of HW words
+    const long per = vec ? C2M_RELABEL_STRIP : C2M_RELABEL_STRIP / C2M_RELABEL_VEC;
+    const long strips = (HW + per - 1) / per;
+    if (strips * P >= (1L << 31)) return (int)hipErrorInvalidValue;
+    const RelabelP p{maps, out, from, to, count, thing_table, HW, (int)strips, label_divisor};
+    const dim3 grid((unsigned)(strips * P));
+    if (vec) hipLaunchKernelGGL(instance_relabel_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(instance_relabel_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+}

@@ -93,6 +93,21 @@ __device__ __forceinline__ int mq_key(int v, int divisor, int C, int ignore, int
     return v < divisor ? cat * divisor : v;                 // cat * divisor + n is v itself at or above the divisor
 }
 
+// `cnt` more pixels of the pair `key` (never 0: the empty slot) -> one image's open-addressing table of P slots.
+__device__ __forceinline__ void mq_pair_add(mq_u64* __restrict__ hkey, int* hcnt, int* overflow, int P, mq_u64 key, int cnt) {
+    const unsigned mask = (unsigned)P - 1u;
+    unsigned slot = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+    for (int i = 0; i < P; ++i, slot = (slot + 1u) & mask) {               // at most max_pairs probes: no unbounded loop
+        mq_u64 cur = __hip_atomic_load(hkey + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0ull) cur = atomicCAS(hkey + slot, 0ull, key);          // a key never changes once it is set
+        if (cur == 0ull || cur == key) {
+            atomicAdd(hcnt + slot, cnt);
+            return;
+        }
+    }
+    atomicOr(overflow, 1);                                                 // the table is full: the pair is dropped
+}
+
 // One distinct (g, p) pair of an image with its pixel count -> the image's tables.
 __device__ void mq_commit(const MqP& a, int img, int g, int p, int cnt) {
     const int K = a.K, C = a.C, div = a.divisor;
@@ -106,18 +121,7 @@ __device__ void mq_commit(const MqP& a, int img, int g, int p, int cnt) {
     if (gc != pc) return;
     if (a.thing[gc] && g == gc * div) { atomicAdd(a.w.crowd_p + t + p, cnt); return; }
     const mq_u64 key = (mq_u64)g * (mq_u64)(K + 1) + (mq_u64)p + 1ull;     // 0 is the empty slot
-    const unsigned mask = (unsigned)a.P - 1u;
-    unsigned slot = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
-    mq_u64* __restrict__ hkey = a.w.hkey + (long)img * a.P;
-    for (int i = 0; i < a.P; ++i, slot = (slot + 1u) & mask) {            // at most max_pairs probes: no unbounded loop
-        mq_u64 cur = __hip_atomic_load(hkey + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0ull) cur = atomicCAS(hkey + slot, 0ull, key);          // a key never changes once it is set
-        if (cur == 0ull || cur == key) {
-            atomicAdd(a.w.hcnt + (long)img * a.P + slot, cnt);
-            return;
-        }
-    }
-    atomicOr(a.w.overflow + img, 1);                                       // the table is full: the pair is dropped
+    mq_pair_add(a.w.hkey + (long)img * a.P, a.w.hcnt + (long)img * a.P, a.w.overflow + img, a.P, key, cnt);
 }
 
 template <typename T>
@@ -267,5 +271,181 @@ C2M_API int c2m_map_quality(const void* pred, const void* gt, int is_u8, const u
     C2M_LAUNCH_CHECK();
     hipLaunchKernelGGL(mq_class_kernel, dim3((unsigned)(N * num_classes)), dim3(64), 0, s, a, tp, fp, fn, iou,
                        (long long*)confusion, overflow);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ tubes
+// Video panoptic quality: a segment is a TUBE, the pixels of one (cat, n) in the k consecutive frames of a window, and the rules
+// above apply to the window as if its frames were one image.  Every table of the count pass is additive over pixels, so the
+// window's tables are the sums of its frames' tables and the pixels are read once, by mq_count_kernel over the B * T frames:
+//
+//   mq_merge_kernel  per window (b, t0) of k frames: area_g, area_p, void_p, crowd_p [K] are summed over the k frames by one
+//                    thread per key, and every occupied slot of the k per-frame pair tables is inserted into the window's table
+//                    with mq_pair_add -- the same key, the same hash, integer atomicCAS / atomicAdd, at most max_pairs probes.
+//                    The window's flag is set when a frame's flag is or when the window's own table fills.
+//   mq_pair_kernel, mq_class_kernel   as they are, on an MqWork of B * (T - k + 1) "images"; k = 1 runs them on the frame tables.
+//   mq_id_kernel     one thread per (window, listed id): the same-id IoU of one named object, by a bounded lookup of (g, g).
+//
+// The window tables are not given a confusion matrix (it has no tube form); mq_class_kernel's copy of it goes to scratch.
+struct MqMergeP {
+    MqWork f, w;                                            // per frame [B * T], per window [B * wpc]
+    int T, k, wpc, K, P, blocks_a, blocks_h;                // wpc = T - k + 1 windows per clip
+};
+
+__global__ __launch_bounds__(256) void mq_merge_kernel(const MqMergeP m) {
+    const int per = m.blocks_a + m.blocks_h;
+    const int win = blockIdx.x / per, blk = blockIdx.x - win * per;
+    const int b = win / m.wpc, t0 = win - b * m.wpc;
+    const long f0 = (long)b * m.T + t0;                                    // the window's first frame; it ends inside clip b
+    if (blk < m.blocks_a) {
+        if (blk == 0 && threadIdx.x == 0) {
+            int any = 0;
+            for (int f = 0; f < m.k; ++f) any |= m.f.overflow[f0 + f];
+            if (any) atomicOr(m.w.overflow + win, 1);
+        }
+        const int j = blk * 256 + threadIdx.x;
+        if (j >= m.K) return;
+        int ag = 0, ap = 0, vp = 0, cp = 0;                                // below 2^31: k * H * W is
+        for (int f = 0; f < m.k; ++f) {
+            const long i = (f0 + f) * m.K + j;
+            ag += m.f.area_g[i]; ap += m.f.area_p[i]; vp += m.f.void_p[i]; cp += m.f.crowd_p[i];
+        }
+        const long o = (long)win * m.K + j;
+        m.w.area_g[o] = ag; m.w.area_p[o] = ap; m.w.void_p[o] = vp; m.w.crowd_p[o] = cp;
+        return;
+    }
+    const int s = (blk - m.blocks_a) * 256 + threadIdx.x;
+    if (s >= m.P) return;
+    for (int f = 0; f < m.k; ++f) {                                        // the key of a frame's slot is the window's key as well
+        const long i = (f0 + f) * m.P + s;
+        const mq_u64 key = m.f.hkey[i];
+        if (key) mq_pair_add(m.w.hkey + (long)win * m.P, m.w.hcnt + (long)win * m.P, m.w.overflow + win, m.P, key, m.f.hcnt[i]);
+    }
+}
+
+// One thread per (window, m): the tube IoU of the object ids[b][m] with the tube of the same id.
+__global__ __launch_bounds__(256) void mq_id_kernel(const MqP a, const int* __restrict__ ids, int M, int wpc, long total,
+                                                    double* __restrict__ id_iou, int* __restrict__ id_gt_area,
+                                                    int* __restrict__ id_pred_area) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long win = i / M;
+    const int m = (int)(i - win * M), b = (int)(win / wpc);
+    const int v = ids[(long)b * M + m], K = a.K;
+    double r = -1.0;
+    int ga = 0, pa = 0;
+    const int g = v < 0 ? K : mq_key(v, a.divisor, a.C, a.ignore, K);
+    if (g != K) {
+        const int gc = g / a.divisor;
+        if (!(a.thing[gc] && g == gc * a.divisor)) {
+            const long t = win * K;
+            ga = a.w.area_g[t + g];
+            pa = a.w.area_p[t + g];
+            if (ga > 0) {
+                const mq_u64 key = (mq_u64)g * (mq_u64)(K + 1) + (mq_u64)g + 1ull;
+                const unsigned mask = (unsigned)a.P - 1u;
+                unsigned slot = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+                long long inter = 0;
+                for (int n = 0; n < a.P; ++n, slot = (slot + 1u) & mask) { // at most max_pairs probes
+                    const mq_u64 cur = a.w.hkey[win * a.P + slot];
+                    if (cur == key) inter = a.w.hcnt[win * a.P + slot];
+                    if (cur == key || cur == 0ull) break;
+                }
+                const long long uni = (long long)pa + ga - inter - a.w.void_p[t + g];    // >= ga > 0
+                r = (double)inter / (double)uni;
+            }
+        }
+    }
+    id_iou[i] = r; id_gt_area[i] = ga; id_pred_area[i] = pa;
+}
+
+// Workspace: the frames' MqWork [B * T] | the windows' MqWork [B * max(T - 1, 1)] | confusion scratch int64 [B * T][(C+1)^2]
+struct TqWork { long frames, windows, conf, bytes; };
+
+static inline long mq_round8(long v) { return (v + 7) & ~7L; }
+
+static inline bool tq_work(long B, long T, int C, int divisor, int max_pairs, TqWork* out) {
+    if (B < 0 || T < 1 || B >= (1L << 24) || T >= (1L << 24) || !mq_sizes_ok(B * T, C, divisor, max_pairs)) return false;
+    const long K = (long)C * divisor, nw = B * (T > 1 ? T - 1 : 1);
+    out->frames = 0;
+    out->windows = mq_round8(mq_work(nullptr, B * T, K, C + 1, max_pairs).bytes);
+    out->conf = out->windows + mq_round8(mq_work(nullptr, nw, K, C + 1, max_pairs).bytes);
+    out->bytes = out->conf + B * T * (long)(C + 1) * (C + 1) * 8;
+    return true;
+}
+
+C2M_API long c2m_tube_quality_workspace_bytes(int B, int T, int num_classes, int label_divisor, int max_pairs) {
+    TqWork t;
+    return tq_work(B, T, num_classes, label_divisor, max_pairs, &t) ? t.bytes : -1;
+}
+
+C2M_API int c2m_tube_quality(const void* pred, const void* gt, int is_u8, const uint8_t* thing_table, const int32_t* windows,
+                             int n_windows, int32_t* tp, int32_t* fp, int32_t* fn, double* iou, uint8_t* overflow,
+                             const int32_t* ids, int M, double* id_iou, int32_t* id_gt_area, int32_t* id_pred_area,
+                             void* workspace, long workspace_bytes, int B, int T, int H, int W, int num_classes,
+                             int label_divisor, int ignore_label, int max_pairs, void* stream) {
+    C2M_ENTER();
+    TqWork t;
+    if (H < 1 || W < 1 || ignore_label < 0 || n_windows < 0 || n_windows > T || M < 0 ||
+        !tq_work(B, T, num_classes, label_divisor, max_pairs, &t))
+        return (int)hipErrorInvalidValue;
+    const long HW = (long)H * W, N = (long)B * T;
+    if (HW * T >= (1L << 31)) return (int)hipErrorInvalidValue;           // a window's counts are int32
+    if ((ids != nullptr) != (M > 0)) return (int)hipErrorInvalidValue;
+    if (n_windows && !windows) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n_windows; ++i) {
+        if (windows[i] < 1 || windows[i] > T) return (int)hipErrorInvalidValue;
+        for (int j = 0; j < i; ++j)
+            if (windows[j] == windows[i]) return (int)hipErrorInvalidValue;
+    }
+    if (N == 0 || n_windows == 0) return 0;
+    if (!pred || !gt || !thing_table || !tp || !fp || !fn || !iou || !overflow || !workspace) return (int)hipErrorInvalidValue;
+    if (ids && (!id_iou || !id_gt_area || !id_pred_area)) return (int)hipErrorInvalidValue;
+    if (workspace_bytes < t.bytes || !c2m_aligned(8, workspace)) return (int)hipErrorInvalidValue;
+    const int K = num_classes * label_divisor;
+    const long bpi = (HW + C2M_MQ_BLOCK_PIX - 1) / C2M_MQ_BLOCK_PIX;
+    const int pb = (max_pairs + 255) / 256, kb = (K + 255) / 256;
+    if ((long)(pb + kb) * N >= (1L << 31) || N * num_classes >= (1L << 31) || N * (M > 0 ? M : 1) >= (1L << 31) * 256)
+        return (int)hipErrorInvalidValue;
+
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)workspace;
+    const MqWork wf = mq_work(base + t.frames, N, K, num_classes + 1, max_pairs);
+    long long* conf_scratch = (long long*)(base + t.conf);
+    hipError_t e = c2m_zero_async(base + t.frames, wf.bytes, s);
+    if (e != hipSuccess) return (int)e;
+    long blocks = C2M_MQ_COUNT_BLOCKS / N;                                 // the count pass of c2m_map_quality over the B * T frames
+    blocks = blocks < 1 ? 1 : (blocks > bpi ? bpi : blocks);
+    const MqP af{pred, gt, thing_table, wf, HW, num_classes, label_divisor, ignore_label, K, max_pairs, (int)blocks, (int)bpi};
+    if (is_u8) hipLaunchKernelGGL(mq_count_kernel<uint8_t>, dim3((unsigned)(blocks * N)), dim3(256), 0, s, af);
+    else hipLaunchKernelGGL(mq_count_kernel<int32_t>, dim3((unsigned)(blocks * N)), dim3(256), 0, s, af);
+    C2M_LAUNCH_CHECK();
+
+    long off = 0;                                                          // windows written so far
+    for (int i = 0; i < n_windows; ++i) {
+        const int k = windows[i], wpc = T - k + 1;
+        const long nw = (long)B * wpc;
+        MqP a = af;
+        if (k > 1) {
+            a.w = mq_work(base + t.windows, nw, K, num_classes + 1, max_pairs);
+            e = c2m_zero_async(base + t.windows, a.w.bytes, s);
+            if (e != hipSuccess) return (int)e;
+            const MqMergeP m{wf, a.w, T, k, wpc, K, max_pairs, kb, pb};
+            hipLaunchKernelGGL(mq_merge_kernel, dim3((unsigned)(nw * (kb + pb))), dim3(256), 0, s, m);
+            C2M_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(mq_pair_kernel, dim3((unsigned)(pb * nw)), dim3(256), 0, s, a, pb);
+        C2M_LAUNCH_CHECK();
+        hipLaunchKernelGGL(mq_class_kernel, dim3((unsigned)(nw * num_classes)), dim3(64), 0, s, a, tp + off * num_classes,
+                           fp + off * num_classes, fn + off * num_classes, iou + off * num_classes, conf_scratch, overflow + off);
+        C2M_LAUNCH_CHECK();
+        if (ids) {
+            const long total = nw * M;
+            hipLaunchKernelGGL(mq_id_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, ids, M, wpc, total,
+                               id_iou + off * M, id_gt_area + off * M, id_pred_area + off * M);
+            C2M_LAUNCH_CHECK();
+        }
+        off += nw;
+    }
     return (int)hipGetLastError();
 }

@@ -454,6 +454,147 @@ class MapScore:
         return r
 
 
+# ------------------------------------------------------------------------------------------ tube quality: video panoptic quality
+# Identity over time: PQ in which a segment is a tube, the pixels of one id in k consecutive frames (VPQ, Kim et al., CVPR 2020;
+# DESIGN §4.2s).  Two objects of one class that swap ids are true positives in every frame and, from k = 2 on, two false
+# positives and two false negatives.
+TUBE_WINDOWS = (1, 2, 3, 4)
+_TUBE_KEYS = ("tp", "fp", "fn", "iou")
+
+
+def _tube_windows(windows, T):
+    """The `windows` argument -> a tuple of distinct ints in 1..T ("all" is T)."""
+    if isinstance(windows, (str, int)) or not hasattr(windows, "__iter__"):
+        windows = (windows,)
+    ks = []
+    for k in windows:
+        if isinstance(k, str):
+            if k != "all":
+                raise ValueError(f"windows holds {k!r}: an entry is an int in 1..T or \"all\"")
+            k = T
+        elif isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"windows holds {k!r}: an entry is an int in 1..T or \"all\"")
+        k = int(k)
+        if not 1 <= k <= T:
+            raise ValueError(f"a window of {k} frames in clips of {T}: windows must lie in 1..{T}")
+        if k in ks:
+            raise ValueError(f"windows holds the length {k} twice")
+        ks.append(k)
+    if not ks:
+        raise ValueError("windows is empty")
+    return tuple(ks)
+
+
+def tube_quality(pred_maps, gt_maps, windows=TUBE_WINDOWS, ids=None, **params):
+    """Video panoptic quality counts of predicted clips against the real ones (ops.tube_quality), on the device: for every k of
+    `windows` and every window of k consecutive frames of a clip, map_quality's counts with a TUBE for a segment -- the pixels
+    of the window with one (cat, n), matched by tube IoU > 0.5.  pred_maps / gt_maps: int32 or uint8 [B,T,H,W] or [B,1,T,H,W]
+    of one dtype and, the channel axis aside, one shape, with map_quality's encodings; both must be in ONE id space over time
+    (a rollout's instance_mask against tracking.anchor_maps of the real frames).  windows: ints in 1..T or "all" (= T), no
+    length twice.  ids: None or int32 [B,M] map values on the device (negative: padding), the objects whose own tube IoU is
+    wanted.  Keyword parameters as map_quality's (MAP_QUALITY); max_pairs also bounds a window's pair table.
+    Returns {k: dict} of device tensors: tp, fp, fn int32 [B,T-k+1,C]; iou float64 [B,T-k+1,C]; overflow bool [B,T-k+1] (a
+    frame of the window or the window itself had more distinct segment pairs than max_pairs; TubeScore.update refuses it) and,
+    with ids, id_iou float64 [B,T-k+1,M] -- the IoU of the predicted and the real tube of that id, not thresholded; -1.0 for
+    padding, a void or crowd id and an object without real pixels in the window -- and id_gt_area, id_pred_area int32."""
+    p = _map_params("tube_quality", params)
+    for name, t in (("pred_maps", pred_maps), ("gt_maps", gt_maps)):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (4, 5) or (t.dim() == 5 and t.shape[1] != 1):
+            raise ValueError(f"{name} must be [B,T,H,W] or [B,1,T,H,W], got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    pred, gt = (t[:, 0] if t.dim() == 5 else t for t in (pred_maps, gt_maps))
+    if pred.shape != gt.shape:
+        raise ValueError(f"pred_maps {tuple(pred_maps.shape)} and gt_maps {tuple(gt_maps.shape)} differ in shape")
+    if pred.shape[1] < 1:
+        raise ValueError("clips without a frame")
+    ks = _tube_windows(windows, int(pred.shape[1]))
+    return ops.tube_quality(pred.contiguous(), gt.contiguous(), ks, ids, **p)
+
+
+class TubeScore:
+    """Sums of tube_quality results over a dataset and video panoptic quality from them, as Cityscapes-VPS aggregates it: per
+    window length k the counts of all windows of all updates are added and PQStat.pq_average gives PQ / SQ / RQ over All /
+    Things / Stuff; `vpq` is the mean over k of the per-k PQ.  With ids, the mean id_iou over the entries >= 0 per k."""
+
+    def __init__(self, **params):
+        p = _map_params("TubeScore", params)
+        self.num_classes, self.max_pairs = int(p["num_classes"]), int(p["max_pairs"])
+        self.things = tuple(sorted(set(int(c) for c in p["thing_list"])))
+        self.params = p
+        self.total = None                                    # {k: sums}, fixed by the first update
+        self.windows = 0
+
+    def _zero(self):
+        C = self.num_classes
+        return {"tp": np.zeros(C, np.int64), "fp": np.zeros(C, np.int64), "fn": np.zeros(C, np.int64),
+                "iou": np.zeros(C, np.float64), "windows": 0, "id_sum": 0.0, "id_n": 0}
+
+    def update(self, result):
+        C = self.num_classes
+        if not isinstance(result, dict) or not result or not all(isinstance(k, (int, np.integer)) for k in result):
+            raise ValueError("a tube_quality result is a dict {k: {...}} with one entry per window length")
+        if self.total is not None and set(self.total) != set(int(k) for k in result):
+            raise ValueError(f"results with different window lengths: {sorted(self.total)} and {sorted(result)}")
+        host = {}
+        for k, r in result.items():
+            h = {n: (r[n].cpu().numpy() if isinstance(r[n], torch.Tensor) else np.asarray(r[n]))
+                 for n in _TUBE_KEYS + ("overflow",) + (("id_iou",) if "id_iou" in r else ())}
+            over = h["overflow"].astype(bool)
+            if over.any():
+                raise ValueError(f"{int(over.sum())} window(s) of {int(k)} frame(s) had more distinct segment pairs than max_pairs="
+                                 f"{self.max_pairs}: their counts are incomplete; call tube_quality with a larger max_pairs")
+            if h["tp"].ndim != 3 or h["tp"].shape[-1] != C:
+                raise ValueError(f"result of shape {h['tp'].shape} for k={int(k)}; the score has {C} classes and takes [B,T-k+1,C]")
+            host[int(k)] = h
+        if self.total is None:
+            self.total = {k: self._zero() for k in host}
+        for k, h in host.items():
+            acc = self.total[k]
+            rows = {n: h[n].reshape(-1, C) for n in _TUBE_KEYS}
+            for i in range(rows["tp"].shape[0]):             # iou: one float64 addition per class and window, in arrival order
+                for n in _TUBE_KEYS:
+                    acc[n] += rows[n][i]
+            acc["windows"] += rows["tp"].shape[0]
+            self.windows += rows["tp"].shape[0]
+            if "id_iou" in h:
+                v = h["id_iou"].astype(np.float64).reshape(-1)
+                for x in v[v >= 0]:
+                    acc["id_sum"] += float(x)
+                acc["id_n"] += int((v >= 0).sum())
+
+    def result(self):
+        out = {"windows": self.windows, "per_k": {}}
+        for k, acc in sorted((self.total or {}).items()):
+            s = {"windows": acc["windows"]}
+            for name, isthing in _PQ_GROUPS:
+                classes = [c for c in range(self.num_classes) if isthing is None or (c in self.things) == isthing]
+                s[name], per_class = pq_average(acc["tp"], acc["fp"], acc["fn"], acc["iou"], classes)
+                if name == "All":
+                    s["per_class"] = per_class
+            s["id_iou"] = acc["id_sum"] / acc["id_n"] if acc["id_n"] else None
+            s["id_n"] = acc["id_n"]
+            out["per_k"][k] = s
+        n = len(out["per_k"])
+        for name, _ in _PQ_GROUPS:
+            key = "vpq" if name == "All" else f"vpq_{name.lower()}"
+            out[key] = sum(s[name]["pq"] for s in out["per_k"].values()) / n if n else 0.0
+        return out
+
+    def write(self, path):
+        r = self.result()
+        with open(path, "a") as f:
+            f.write(f"windows {r['windows']}\n")
+            f.write(f"vpq {r['vpq']} vpq_things {r['vpq_things']} vpq_stuff {r['vpq_stuff']}\n")
+            for k, s in r["per_k"].items():
+                for name, _ in _PQ_GROUPS:
+                    g = s[name]
+                    f.write(f"k{k}_{name} pq {g['pq']} sq {g['sq']} rq {g['rq']} n {g['n']}\n")
+                if s["id_iou"] is not None:
+                    f.write(f"k{k}_id_iou {s['id_iou']} n {s['id_n']}\n")
+            f.write("\n\n")
+        return r
+
+
 # ------------------------------------------------------------------------------------------ flow scores: endpoint error and consistency
 # What optical-flow work reports (Sintel's EPE and speed buckets, KITTI's Fl, Barron's angular error) and, for clips without
 # ground truth, what the flows say about themselves: the photometric error of the warp and the forward-backward distance

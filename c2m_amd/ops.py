@@ -2742,6 +2742,78 @@ def instance_match(pairs, ref_slots, ref_count, frame_slots, frame_count, min_io
     return link
 
 
+_RelabelPlan = collections.namedtuple("_RelabelPlan", "P HW table things label_divisor")
+
+
+def _instance_relabel_plan(maps, pairs_from, pairs_to, count, thing_list, label_divisor):
+    """Every check of instance_relabel, made before anything is launched (host tensors pass: the device is the launch path's
+    check), and the host half of it: each plane's pairs sorted by `from` and padded to the kernel's 64 -> table, flat int32:
+    from [P, 64] | to [P, 64] | count [P]."""
+    if not isinstance(maps, torch.Tensor) or maps.dtype != torch.int32 or maps.dim() < 3:
+        raise ValueError("maps must be an int32 tensor [..., H, W] with at least one leading axis, got "
+                         f"{(maps.dtype, tuple(maps.shape)) if isinstance(maps, torch.Tensor) else type(maps).__name__}")
+    if not maps.is_contiguous():
+        raise ValueError("maps must be contiguous")
+    H, W = maps.shape[-2:]
+    P = int(np.prod(maps.shape[:-2]))
+    if H * W >= 2 ** 31 or P >= 2 ** 24:
+        raise ValueError(f"{P} planes of {H}x{W} pixels: too many planes or too large a plane (H * W must be below 2**31)")
+    try:
+        label_divisor = int(label_divisor)
+        things = tuple(sorted(set(int(c) for c in thing_list)))
+    except (TypeError, ValueError):
+        raise ValueError("label_divisor must be an integer and thing_list a list of class ids") from None
+    if not 1 <= label_divisor < 2 ** 31:
+        raise ValueError(f"label_divisor must be in 1..2**31-1, got {label_divisor}")
+    if any(not 0 <= c <= 255 for c in things):
+        raise ValueError(f"thing_list must lie in 0..255, got {list(thing_list)}")
+    cap = 64                                                      # c2m_instance_link_max_nodes(): one LDS list per plane
+    frm, to, cnt = (np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in (pairs_from, pairs_to, count))
+    if frm.ndim != 2 or frm.shape != to.shape or frm.shape[0] != P or frm.shape[1] > cap or cnt.shape != (P,) or \
+            any(a.dtype.kind not in "iu" for a in (frm, to, cnt)):
+        raise ValueError(f"pairs_from and pairs_to must be integer [P={P}, n <= {cap}] and count [P={P}], got {frm.shape}, "
+                         f"{to.shape} and {cnt.shape}")
+    n = frm.shape[1]
+    if cnt.size and (cnt.min() < 0 or cnt.max() > n):
+        raise ValueError(f"count must lie in 0..{n}")
+    live = np.arange(n)[None] < cnt[:, None]                      # also the live entries after the sort: padding sorts last
+    frm, to = frm.astype(np.int64), to.astype(np.int64)
+    for a in (frm, to):
+        if live.any() and (a[live].min() < -2 ** 31 or a[live].max() >= 2 ** 31 - 1):
+            raise ValueError("pair values must be int32 below 2**31 - 1 (the list's padding)")
+    key = np.where(live, frm, 2 ** 31 - 1)
+    order = np.argsort(key, axis=1, kind="stable")
+    key = np.take_along_axis(key, order, 1)
+    if n > 1 and ((key[:, 1:] == key[:, :-1]) & live[:, 1:]).any():
+        raise ValueError("a plane lists one `from` value twice: the mapping must be a function")
+    table = np.zeros((2, P, cap), np.int32)
+    table[0, :, :n] = np.where(live, key, 0)
+    table[1, :, :n] = np.where(live, np.take_along_axis(to, order, 1), 0)
+    table = np.concatenate([table.reshape(-1), cnt.astype(np.int32)])
+    return _RelabelPlan(P, H * W, table, things, label_divisor)
+
+
+def instance_relabel(maps, pairs_from, pairs_to, count, thing_list, label_divisor=1000):
+    """Every plane of int32 maps [..., H, W] rewritten through its own list of (from, to) pairs (csrc/instance_link.hip:
+    c2m_instance_relabel; the contract is in include/c2m_hip.h): a value equal to a `from` becomes its `to`, all at once (two ids
+    may swap); every other thing value (v >= label_divisor, v // label_divisor in thing_list) becomes its class's crowd id
+    (v // label_divisor) * label_divisor; stuff and void stay.  pairs_from, pairs_to: host integers [P, n <= 64], count [P] (the
+    pairs of plane p are the first count[p]; any order).  Returns a new tensor of the shape of maps; one upload and one launch on
+    the current stream."""
+    pl = _instance_relabel_plan(maps, pairs_from, pairs_to, count, thing_list, label_divisor)
+    _hip_only(maps)
+    _on_current_device(maps)
+    maps = maps.detach()
+    out = torch.empty_like(maps)
+    if pl.P and pl.HW:
+        thing, _ = _panoptic_tables(pl.things, maps.device)
+        tab = torch.from_numpy(pl.table).to(maps.device)
+        n = pl.P * 64
+        _lib.check(_lib.lib().c2m_instance_relabel(_p(maps), _p(out), _p(tab[:n]), _p(tab[n:2 * n]), _p(tab[2 * n:]), _p(thing),
+                                                   pl.P, pl.HW, pl.label_divisor, _stream()), "instance_relabel")
+    return out
+
+
 def occlusion_splat(flow, want_map=True, want_clip=False):
     """get_occlusion_map for [B,2,H,W] or, frame-batched, [B,2,T,H,W] flows -> ([B,1,(T,)H,W] map, clip_mask) ."""
     _dev(flow)
@@ -3772,6 +3844,94 @@ def map_quality(pred, gt, num_classes, thing_list, label_divisor, ignore_label, 
                                      _p(over), _p(work), nbytes, N, pl.H, pl.W, C, pl.label_divisor, pl.ignore_label,
                                      pl.max_pairs, _stream()), "map_quality")
     return {"tp": tp, "fp": fp, "fn": fn, "iou": iou, "confusion": conf, "overflow": over.view(torch.bool)}
+
+
+# ------------------------------------------------------------------------------------------ scoring of label maps over time
+# (csrc/map_quality.hip; c2m_amd.evaluate.tube_quality is the public interface)
+_TubeQualityPlan = collections.namedtuple("_TubeQualityPlan", "B T H W windows M mq")
+
+
+def _tube_quality_plan(pred, gt, windows, ids, num_classes, thing_list, label_divisor, ignore_label, max_pairs):
+    """Every check of tube_quality, made before anything is launched (host tensors pass: the device is the launch path's
+    check).  pred, gt: [B,T,H,W], both int32 or both uint8; windows: distinct ints in 1..T; ids: None or int32 [B,M]."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 4:
+            raise ValueError(f"{name} must be [B,T,H,W], got {tuple(t.shape)}")
+    if not (pred.is_contiguous() and gt.is_contiguous()):
+        raise ValueError("pred and gt must be contiguous")
+    B, T, H, W = pred.shape
+    if T < 1:
+        raise ValueError(f"clips of {T} frames: a clip needs at least one frame")
+    frames = lambda t: t.view(t.shape[0] * t.shape[1], t.shape[2], t.shape[3])
+    mq = _map_quality_plan(frames(pred), frames(gt), num_classes, thing_list, label_divisor, ignore_label, max_pairs)
+    try:
+        ks = tuple(int(k) for k in windows)
+        if any(isinstance(k, (bool, float)) for k in windows):
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"windows must be a sequence of frame counts, got {windows!r}") from None
+    if not ks:
+        raise ValueError("windows is empty")
+    for k in ks:
+        if not 1 <= k <= T:
+            raise ValueError(f"a window of {k} frames in clips of {T}: windows must lie in 1..{T}")
+    if len(set(ks)) != len(ks):
+        raise ValueError(f"windows holds a length twice: {list(ks)}")
+    if T * H * W >= 2 ** 31:
+        raise ValueError(f"clips of {T} frames of {H}x{W} pixels: a tube's pixel counts are int32 (T * H * W must be below 2**31)")
+    M = 0
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
+            raise ValueError(f"ids must be an int32 tensor [B={B}, M >= 1], got "
+                             f"{(ids.dtype, tuple(ids.shape)) if isinstance(ids, torch.Tensor) else type(ids).__name__}")
+        M = int(ids.shape[1])
+    return _TubeQualityPlan(B, T, H, W, ks, M, mq)
+
+
+def tube_quality(pred, gt, windows, ids, num_classes, thing_list, label_divisor, ignore_label, max_pairs):
+    """Video panoptic quality counts of B predicted clips against B ground-truth ones, per window of k consecutive frames, for
+    every k of `windows` (csrc/map_quality.hip; the contract is in include/c2m_hip.h and DESIGN.md 4.2s).  pred, gt: int32 or
+    uint8 [B,T,H,W]; ids: None or int32 [B,M] map values (negative: padding).  Returns {k: dict} of device tensors: tp, fp, fn
+    int32 [B,T-k+1,C], iou float64 [B,T-k+1,C], overflow bool [B,T-k+1] and, with ids, id_iou float64 and id_gt_area,
+    id_pred_area int32 [B,T-k+1,M].  The pixels are read once; everything runs on the current stream, nothing is read back."""
+    pl = _tube_quality_plan(pred, gt, windows, ids, num_classes, thing_list, label_divisor, ignore_label, max_pairs)
+    _hip_only(pred, gt, ids)
+    _on_current_device(pred, gt, ids)
+    L = _lib.lib()
+    dev, B, T, C, M, mq = pred.device, pl.B, pl.T, pl.mq.num_classes, pl.M, pl.mq
+    pred, gt = pred.detach(), gt.detach()
+    ids = None if ids is None else _f(ids.detach())
+    table, _ = _panoptic_tables(mq.things, dev)
+    counts = [B * (T - k + 1) for k in pl.windows]
+    total = sum(counts)
+    tp, fp, fn = (torch.zeros(total, C, device=dev, dtype=torch.int32) for _ in range(3))
+    iou = torch.zeros(total, C, device=dev, dtype=torch.float64)
+    over = torch.zeros(total, device=dev, dtype=torch.uint8)
+    id_iou = torch.full((total, M), -1.0, device=dev, dtype=torch.float64) if M else None
+    id_ga, id_pa = (torch.zeros(total, M, device=dev, dtype=torch.int32) if M else None for _ in range(2))
+    if B:
+        nbytes = L.c2m_tube_quality_workspace_bytes(B, T, C, mq.label_divisor, mq.max_pairs)
+        if nbytes < 0:
+            raise ValueError(f"tube_quality: sizes out of range (B={B}, T={T}, num_classes={C}, label_divisor={mq.label_divisor}, "
+                             f"max_pairs={mq.max_pairs})")
+        work = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.int64)
+        ks = (ctypes.c_int32 * len(pl.windows))(*pl.windows)
+        _lib.check(L.c2m_tube_quality(_p(pred), _p(gt), int(mq.u8), _p(table), ks, len(pl.windows), _p(tp), _p(fp), _p(fn), _p(iou),
+                                      _p(over), _p(ids), M, _p(id_iou), _p(id_ga), _p(id_pa), _p(work), nbytes, B, T, pl.H, pl.W, C,
+                                      mq.label_divisor, mq.ignore_label, mq.max_pairs, _stream()), "tube_quality")
+    out, off = {}, 0
+    for k, n in zip(pl.windows, counts):
+        lead = (B, T - k + 1)
+        r = {"tp": tp[off:off + n].view(*lead, C), "fp": fp[off:off + n].view(*lead, C), "fn": fn[off:off + n].view(*lead, C),
+             "iou": iou[off:off + n].view(*lead, C), "overflow": over[off:off + n].view(torch.bool).view(*lead)}
+        if M:
+            r.update(id_iou=id_iou[off:off + n].view(*lead, M), id_gt_area=id_ga[off:off + n].view(*lead, M),
+                     id_pred_area=id_pa[off:off + n].view(*lead, M))
+        out[k] = r
+        off += n
+    return out
 
 
 # =============================================================================================== connected components, instances

@@ -203,6 +203,44 @@ def tracks_from_links(ids, edges, valid, count, overflow, num_input_frames, id_r
     return out
 
 
+def anchor_pairs(tracks, num_input_frames):
+    """Tracks -> (from [B*T, max_nodes], to [B*T, max_nodes], count [B*T]) int64 on the host: for plane (b, t) the pairs
+    (tracks.ids[b, n, t], tracks.ids[b, n, num_input_frames - 1]) of the nodes n < count[b]."""
+    ids = tracks.ids.numpy().astype(np.int64)                               # [B, M, T]
+    B, M, T = ids.shape
+    if not 1 <= int(num_input_frames) <= T:
+        raise ValueError(f"num_input_frames={num_input_frames} but the tracks have {T} frames")
+    frm = ids.transpose(0, 2, 1).reshape(B * T, M)
+    to = np.broadcast_to(ids[:, None, :, int(num_input_frames) - 1], (B, T, M)).reshape(B * T, M)
+    count = np.repeat(tracks.count.numpy().astype(np.int64), T)
+    return frm, np.ascontiguousarray(to), count
+
+
+def anchor_maps(instance_mask, tracks, num_input_frames, thing_list=tuple(range(11, 19)), label_divisor=1000):
+    """The instance maps of the real frames in the id space of the ANCHOR (the last input frame), on the device: what a rollout's
+    maps, which carry the anchor's ids through the predicted frames, are scored against (evaluate.tube_quality).
+
+    instance_mask [B,1,T,H,W] or [B,T,H,W] int32 on the device; tracks: track_instances' result for the same maps.  In plane
+    (b, t) a value equal to tracks.ids[b, n, t] of a node n < count[b] becomes tracks.ids[b, n, num_input_frames - 1]; every
+    other thing value (v >= label_divisor, v // label_divisor in thing_list) becomes its class's crowd id (v // label_divisor) *
+    label_divisor -- an object the anchor does not know, or one whose track broke, neither rewards nor punishes a prediction that
+    could not contain it; stuff and void stay.  The mapping is simultaneous (two objects may swap ids).  Returns a new tensor of
+    the input's shape (ops.instance_relabel: one upload, one launch on the current stream)."""
+    if not isinstance(instance_mask, torch.Tensor) or instance_mask.dim() not in (4, 5) or \
+            (instance_mask.dim() == 5 and instance_mask.shape[1] != 1):
+        raise ValueError(f"instance maps must be [B,1,T,H,W] or [B,T,H,W], got {list(getattr(instance_mask, 'shape', ()))}")
+    if instance_mask.dtype != torch.int32:
+        raise TypeError(f"instance maps must be int32, got {instance_mask.dtype}")
+    if not isinstance(tracks, Tracks):
+        raise TypeError(f"tracks must be a Tracks, got {type(tracks).__name__}")
+    B, T = instance_mask.shape[0], instance_mask.shape[-3]
+    if tuple(tracks.ids.shape[::2]) != (B, T) or tuple(tracks.count.shape) != (B,):
+        raise ValueError(f"tracks of {tracks.ids.shape[0]} samples and {tracks.ids.shape[2]} frames for maps of {B} and {T}")
+    frm, to, count = anchor_pairs(tracks, num_input_frames)
+    maps = instance_mask if instance_mask.is_contiguous() else instance_mask.contiguous()
+    return ops.instance_relabel(maps, frm, to, count, thing_list, label_divisor)
+
+
 def scene_graphs(tr, size, num_input_frames, lambda_traj=1):
     """Tracks -> (tracking_ids [B] of [T, N] int64, graphs [B] of graph.GraphData), per sample what graph.scene_graph returns
     for tracker files with the same boxes: pixel edges become tracker boxes (interactive.edges_to_tracker), the rest is

@@ -757,6 +757,42 @@ int c2m_map_quality(const void* pred, const void* gt, int is_u8, const uint8_t* 
                     int32_t* fn, double* iou, int64_t* confusion, uint8_t* overflow, void* workspace, long workspace_bytes,
                     int N, int H, int W, int num_classes, int label_divisor, int ignore_label, int max_pairs, void* stream);
 
+/* ---- Scoring of label maps over time (map_quality.hip; c2m_amd.evaluate.tube_quality) -----------------------------------------
+ * Video panoptic quality: the counts above with a TUBE for a segment.  pred, gt: clips [B][T][H][W] with the encodings and
+ * parameters of c2m_map_quality.  A window (b, t0, k) is frames t0 .. t0 + k - 1 of clip b (never across a clip); a tube segment
+ * is the pixels of the window with one non-void (cat, n); the rules above apply to the window as if it were one image of k * H
+ * rows.  windows: HOST int32 [n_windows], distinct k in 1..T.  The outputs hold the results of windows[0], then windows[1], ...:
+ * with nw(k) = B * (T - k + 1) windows for k, in the order (b, t0), tp, fp, fn are int32 [sum nw][C], iou float64 [sum nw][C],
+ * overflow uint8 [sum nw] (1: a frame of the window had more pairs than max_pairs, or the window's own table of max_pairs slots
+ * filled).  k = 1 equals c2m_map_quality bit for bit.
+ * ids (optional, with M >= 1): device int32 [B][M] map values, negative = padding.  With g the key of ids[b][m], id_iou float64
+ * [sum nw][M] is -1 for padding, a void value, a ground-truth crowd key or a g without ground-truth pixels in the window, else
+ * inter / union with inter = the pixels of the window that hold g in BOTH maps and union = area_p[g] + area_g[g] - inter -
+ * void_p[g]: the same-id IoU, not thresholded.  id_gt_area, id_pred_area int32 [sum nw][M]: area_g[g], area_p[g] (0 where g is
+ * padding, void or a crowd key).  ids == NULL: M must be 0 and the three outputs are not touched.
+ * The pixels are read once: the count pass of c2m_map_quality over the B * T frames, then per k a zero-fill of the window tables,
+ * a merge of the k per-frame tables of every window (sums; the pair tables re-inserted with the same key and hash), and the pair
+ * and class passes of c2m_map_quality on the window tables; k = 1 runs them on the frame tables.  Limits of c2m_map_quality with
+ * N = B * T, and T * H * W < 2^31 (a window's counts are int32).  workspace: c2m_tube_quality_workspace_bytes(B, T, num_classes,
+ * label_divisor, max_pairs) bytes (-1 for sizes out of range), 8-byte aligned.  Everything is checked before the first launch;
+ * all launches on `stream`, no synchronisation, no copy to the host, no loop that waits for another wave.  Integer atomics only:
+ * every output is bit-repeatable.                                                                                               */
+long c2m_tube_quality_workspace_bytes(int B, int T, int num_classes, int label_divisor, int max_pairs);
+int c2m_tube_quality(const void* pred, const void* gt, int is_u8, const uint8_t* thing_table, const int32_t* windows,
+                     int n_windows, int32_t* tp, int32_t* fp, int32_t* fn, double* iou, uint8_t* overflow, const int32_t* ids,
+                     int M, double* id_iou, int32_t* id_gt_area, int32_t* id_pred_area, void* workspace, long workspace_bytes,
+                     int B, int T, int H, int W, int num_classes, int label_divisor, int ignore_label, int max_pairs,
+                     void* stream);
+
+/* ---- Relabelling of instance maps (instance_link.hip; c2m_amd.tracking.anchor_maps) --------------------------------------------
+ * maps, out: int32 [P][H*W] planes (out may not alias maps).  Plane p has n = count[p] <= 64 pairs (from[p][i], to[p][i]), from
+ * strictly ascending over i < n (device int32 [P][64] each).  A value equal to a from becomes its to -- all at once, so two ids
+ * may swap --; every other value v >= label_divisor whose class v / label_divisor is a thing (thing_table: device uint8 [256],
+ * non-zero for a thing; classes above 255 are no things) becomes (v / label_divisor) * label_divisor, its class's crowd id;
+ * everything else (stuff, void, negative values) is copied.  HW < 2^31, label_divisor >= 1.  One launch on `stream`.          */
+int c2m_instance_relabel(const int32_t* maps, int32_t* out, const int32_t* from, const int32_t* to, const int32_t* count,
+                         const uint8_t* thing_table, int P, long HW, int label_divisor, void* stream);
+
 /* ---- rendering (render.hip): results as uint8 pictures on the device ------------------------------------------------
  * A SHEET is uint8 [T][rows*H][cols*W][C] (HWC); sample b sits in cell (b / cols, b % cols), as the reference's merge
  * (utils/utils.py:26-43) lays samples out; cells without a sample hold zero input.  B <= rows * cols.  Inputs are dense
