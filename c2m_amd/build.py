@@ -50,7 +50,7 @@ def build(force=False, verbose=False, variant=None, defines=()):
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     common = [os.path.join(CSRC, h) for h in ("common.h", "wave.h", "instance_compact.h", "dtype.h", "conv_store.h", "conv_types.h", "conv_common.h",
-                                              "warp_coord.h", "flow_sample.h")] + \
+                                              "warp_coord.h", "flow_sample.h", "score_rows.h")] + \
         [os.path.join(os.path.dirname(HERE), "include", h) for h in ("c2m_geom.h", "c2m_hip.h")]   # common.h includes both
     suffix = f"_{variant}" if variant else ""
     lib = LIB.replace(".so", suffix + ".so")

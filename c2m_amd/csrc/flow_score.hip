@@ -32,39 +32,20 @@
 // Launches: one workgroup (256 threads) owns a tile of 1024 consecutive pixels of one pair, four per thread at a stride of 256
 // (coalesced rows; the gathers of the consistency kernel follow the flow from there).  A thread keeps its four pixels' terms
 // in registers; then, for the whole pair and for each region bit, the terms are added in a fixed order -- the thread's four in
-// index order, wave shuffles (wave.h), the four waves in index order from LDS -- into partial[block][9][K].  A second kernel,
-// one workgroup per pair, adds the partials: slice s of eight adds the tiles s, s + 8, ... in order, then the slices are added in
-// index order.  No atomics, nothing read back, bit-repeatable; a pair's sums do not depend on the batch it is in.
+// index order, then the reduction of score_rows.h: wave shuffles, the four waves in index order into partial[block][9][K] and
+// score_reduce_kernel<8, 128>, one workgroup per pair.  No atomics, nothing read back, bit-repeatable; a pair's sums do not
+// depend on the batch it is in.
 // LDS per workgroup: 4 x 90 x 8 = 2,880 bytes (quality), 4 x 63 x 8 = 2,016 (consistency), 8 x 128 x 8 = 8,192 (reduce); no
-// scratch, at most 86 VGPRs: occupancy is not limited by either.
-#include "common.h"
+// scratch, at most 87 VGPRs: occupancy is not limited by either.
+#include "score_rows.h"
 
 #define C2M_FS_THREADS 256
 #define C2M_FS_PPT 4                                        // pixels per thread
 #define C2M_FS_TILE (C2M_FS_THREADS * C2M_FS_PPT)           // 1024 pixels
-#define C2M_FS_ROWS 9                                       // whole pair + 8 region bits
 #define C2M_FQ_COLS 10
 #define C2M_FC_COLS 7
-#define C2M_FS_RED_THREADS 1024
-#define C2M_FS_RED_SLOTS 128                                // >= 9 * 10 values
-#define C2M_FS_RED_SLICES (C2M_FS_RED_THREADS / C2M_FS_RED_SLOTS)
 
-struct FsBf16 { uint16_t bits; };
-
-__device__ __forceinline__ double fs_val(float v) { return (double)v; }
-__device__ __forceinline__ double fs_val(FsBf16 v) { return (double)__uint_as_float((uint32_t)v.bits << 16); }
 __device__ __forceinline__ bool fs_finite(double v) { return fabs(v) < __builtin_huge_val(); }       // false for NaN
-
-// The four waves' rows in index order -> partial[block][rows][COLS]; rows the caller did not fill are zero.
-template <int COLS>
-__device__ __forceinline__ void fs_store_partial(double (*red)[C2M_FS_ROWS * COLS], int nrows, double* __restrict__ partial) {
-    const int tid = threadIdx.x;
-    if (tid < C2M_FS_ROWS * COLS) {
-        double a = 0.0;
-        if (tid < nrows * COLS) a = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        partial[(long)blockIdx.x * (C2M_FS_ROWS * COLS) + tid] = a;
-    }
-}
 
 // pair (b, t) = frame / Tn, frame % Tn; channel c of it starts at b * sB + c * sC + t * sT, HW dense elements.
 template <typename PT>
@@ -72,7 +53,7 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_quality_kernel(
     const PT* __restrict__ pred, const float* __restrict__ target, const uint8_t* __restrict__ valid,
     const uint8_t* __restrict__ regions, int Tn, int HW, long sBp, long sCp, long sTp, long sBt, long sCt, long sTt,
     unsigned tiles, double* __restrict__ partial) {
-    __shared__ double red[C2M_FS_THREADS / 64][C2M_FS_ROWS * C2M_FQ_COLS];
+    __shared__ double red[C2M_FS_THREADS / 64][C2M_SCORE_ROWS * C2M_FQ_COLS];
     const int tid = threadIdx.x;
     const unsigned frame = blockIdx.x / tiles, tile = blockIdx.x - frame * tiles;
     const int b = (int)(frame / (unsigned)Tn), t = (int)(frame - (unsigned)b * Tn);
@@ -94,7 +75,7 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_quality_kernel(
             bool scored = fs_finite(tu) && fs_finite(tv) && fabs(tu) < 1e9 && fabs(tv) < 1e9;
             if (valid != nullptr) scored = scored && valid[mask0 + i] != 0;
             if (scored) {
-                const double pu = fs_val(pu_[i]), pv = fs_val(pv_[i]);
+                const double pu = score_val(pu_[i]), pv = score_val(pv_[i]);
                 unsigned f = 1u;
                 if (fs_finite(pu) && fs_finite(pv)) {
                     const double du = pu - tu, dv = pv - tv;
@@ -116,14 +97,14 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_quality_kernel(
     }
 
     const int lane = tid & 63, wave = tid >> 6;
-    const int nrows = regions != nullptr ? C2M_FS_ROWS : 1;
+    const int nrows = regions != nullptr ? C2M_SCORE_ROWS : 1;
     for (int k = 0; k < nrows; ++k) {
         int c0 = 0, c1 = 0;                                 // three 10-bit counts each: a wave holds at most 256 pixels
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
         for (int j = 0; j < C2M_FS_PPT; ++j) {
             const unsigned f = flag[j];
-            const bool m = (f & 1u) && (k == 0 || ((f >> (7 + k)) & 1u));
+            const bool m = (f & 1u) && C2M_SCORE_ROW_HAS(k, f >> 8);
             if (m) {
                 c0 += 1 + (int)((f >> 1) & 1u) * (1 << 10) + (int)((f >> 2) & 1u) * (1 << 20);
                 c1 += (int)((f >> 3) & 1u) + (int)((f >> 4) & 1u) * (1 << 10) + (int)((f >> 5) & 1u) * (1 << 20);
@@ -154,7 +135,7 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_quality_kernel(
         }
     }
     __syncthreads();
-    fs_store_partial<C2M_FQ_COLS>(red, nrows, partial);
+    score_store_partial<C2M_FQ_COLS>(red, nrows, partial);
 }
 
 // The four corners and the two weights of the bilinear sample at (yx, yy), 0 <= yx <= W - 1 and 0 <= yy <= H - 1.
@@ -175,8 +156,8 @@ __device__ __forceinline__ FsTap fs_tap(double yx, double yy, int H, int W) {
 
 template <typename T>
 __device__ __forceinline__ double fs_sample(const T* __restrict__ img, const FsTap& t) {
-    const double top = fs_val(img[t.o00]) * (1.0 - t.ax) + fs_val(img[t.o01]) * t.ax;
-    const double bot = fs_val(img[t.o10]) * (1.0 - t.ax) + fs_val(img[t.o11]) * t.ax;
+    const double top = score_val(img[t.o00]) * (1.0 - t.ax) + score_val(img[t.o01]) * t.ax;
+    const double bot = score_val(img[t.o10]) * (1.0 - t.ax) + score_val(img[t.o11]) * t.ax;
     return top * (1.0 - t.ay) + bot * t.ay;
 }
 
@@ -188,7 +169,7 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_consistency_kernel(
     const float* __restrict__ fab, const T* __restrict__ ia, const T* __restrict__ ib, const float* __restrict__ fba,
     const uint8_t* __restrict__ regions, int Tn, int H, int W, FsStrides st, double alpha1, double alpha2, unsigned tiles,
     float* __restrict__ photo_map, float* __restrict__ fb_map, uint8_t* __restrict__ incons_map, double* __restrict__ partial) {
-    __shared__ double red[C2M_FS_THREADS / 64][C2M_FS_ROWS * C2M_FC_COLS];
+    __shared__ double red[C2M_FS_THREADS / 64][C2M_SCORE_ROWS * C2M_FC_COLS];
     const int tid = threadIdx.x;
     const int HW = H * W;
     const unsigned frame = blockIdx.x / tiles, tile = blockIdx.x - frame * tiles;
@@ -221,7 +202,7 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_consistency_kernel(
                 const FsTap tap = fs_tap(yx, yy, H, W);
                 double s = 0.0;
 #pragma unroll
-                for (int c = 0; c < C; ++c) s += fabs(fs_val(a_[c * st.s[1][1] + i]) - fs_sample(b_ + c * st.s[2][1], tap));
+                for (int c = 0; c < C; ++c) s += fabs(score_val(a_[c * st.s[1][1] + i]) - fs_sample(b_ + c * st.s[2][1], tap));
                 const double p = s / (double)C;
                 ph[j] = p;
                 pm = (float)p;
@@ -247,14 +228,14 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_consistency_kernel(
     }
 
     const int lane = tid & 63, wave = tid >> 6;
-    const int nrows = regions != nullptr ? C2M_FS_ROWS : 1;
+    const int nrows = regions != nullptr ? C2M_SCORE_ROWS : 1;
     for (int k = 0; k < nrows; ++k) {
         int c0 = 0;                                         // three 10-bit counts
         double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
         for (int j = 0; j < C2M_FS_PPT; ++j) {
             const unsigned f = flag[j];
-            const bool m = (f & 1u) && (k == 0 || ((f >> (7 + k)) & 1u));
+            const bool m = (f & 1u) && C2M_SCORE_ROW_HAS(k, f >> 8);
             if (m) c0 += 1 + (int)((f >> 1) & 1u) * (1 << 10) + (int)((f >> 2) & 1u) * (1 << 20);
             s0 += m ? ph[j] : 0.0;
             s1 += m ? ph[j] * ph[j] : 0.0;
@@ -278,43 +259,17 @@ __global__ __launch_bounds__(C2M_FS_THREADS) void flow_consistency_kernel(
         }
     }
     __syncthreads();
-    fs_store_partial<C2M_FC_COLS>(red, nrows, partial);
-}
-
-// One workgroup per pair: value v = tid & 127 (< vals = 9 * cols), slice s = tid >> 7 adds the tiles s, s + 8, ... in order; the
-// eight slices are then added in index order.  Columns nan_from .. cols - 1 are written as NaN (nan_from = cols: none).
-__global__ __launch_bounds__(C2M_FS_RED_THREADS) void flow_score_reduce_kernel(const double* __restrict__ partial, int tiles,
-                                                                               int vals, int cols, int nan_from,
-                                                                               double* __restrict__ out) {
-    __shared__ double acc[C2M_FS_RED_SLICES][C2M_FS_RED_SLOTS];
-    const int v = threadIdx.x & (C2M_FS_RED_SLOTS - 1), s = threadIdx.x / C2M_FS_RED_SLOTS;
-    const double* __restrict__ p = partial + (long)blockIdx.x * tiles * vals;
-    if (v < vals) {
-        double a = 0.0;
-#pragma unroll 4
-        for (int i = s; i < tiles; i += C2M_FS_RED_SLICES) a += p[(long)i * vals + v];
-        acc[s][v] = a;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < vals) {
-        double a = 0.0;
-        for (int i = 0; i < C2M_FS_RED_SLICES; ++i) a += acc[i][threadIdx.x];
-        if ((int)threadIdx.x % cols >= nan_from) a = __builtin_nan("");
-        out[(long)blockIdx.x * vals + threadIdx.x] = a;
-    }
+    score_store_partial<C2M_FC_COLS>(red, nrows, partial);
 }
 
 static long fs_tiles(int H, int W) { return ((long)H * W + C2M_FS_TILE - 1) / C2M_FS_TILE; }
 
-static long fs_workspace_bytes(int B, int T, int H, int W, int cols) {
-    if (B < 0 || T < 0 || H < 1 || W < 1) return -1;
-    return (long)B * T * fs_tiles(H, W) * C2M_FS_ROWS * cols * (long)sizeof(double);
+C2M_API long c2m_flow_quality_workspace_bytes(int B, int T, int H, int W) {
+    return score_workspace_bytes(B, T, H, W, fs_tiles(H, W), C2M_FQ_COLS);
 }
 
-C2M_API long c2m_flow_quality_workspace_bytes(int B, int T, int H, int W) { return fs_workspace_bytes(B, T, H, W, C2M_FQ_COLS); }
-
 C2M_API long c2m_flow_consistency_workspace_bytes(int B, int T, int H, int W) {
-    return fs_workspace_bytes(B, T, H, W, C2M_FC_COLS);
+    return score_workspace_bytes(B, T, H, W, fs_tiles(H, W), C2M_FC_COLS);
 }
 
 // (B, C, T) strides of one operand: none negative, and the channels of a pair apart by at least a plane.
@@ -330,10 +285,10 @@ C2M_API int c2m_flow_quality(const void* pred, const float* target, const uint8_
         return (int)hipErrorInvalidValue;
     const long frames = (long)B * T, plane = (long)H * W;
     if (frames == 0) return 0;
-    if (plane > 0x7fffffffL || frames > 0x7fffffffL || frames * fs_tiles(H, W) > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    if (!score_sizes_ok(frames, plane, fs_tiles(H, W))) return (int)hipErrorInvalidValue;
     const long blocks = frames * fs_tiles(H, W);
     if (pred == nullptr || target == nullptr || out == nullptr || workspace == nullptr ||
-        workspace_bytes < fs_workspace_bytes(B, T, H, W, C2M_FQ_COLS) || !fs_strides_ok(pred_strides, plane, 2) ||
+        workspace_bytes < c2m_flow_quality_workspace_bytes(B, T, H, W) || !fs_strides_ok(pred_strides, plane, 2) ||
         !fs_strides_ok(target_strides, plane, 2))
         return (int)hipErrorInvalidValue;
     double* partial = (double*)workspace;
@@ -345,13 +300,11 @@ C2M_API int c2m_flow_quality(const void* pred, const float* target, const uint8_
                            target, valid, regions, T, (int)plane, sp[0], sp[1], sp[2], st[0], st[1], st[2],
                            (unsigned)fs_tiles(H, W), partial);
     else
-        hipLaunchKernelGGL((flow_quality_kernel<FsBf16>), dim3((unsigned)blocks), dim3(C2M_FS_THREADS), 0, s,
-                           (const FsBf16*)pred, target, valid, regions, T, (int)plane, sp[0], sp[1], sp[2], st[0], st[1], st[2],
+        hipLaunchKernelGGL((flow_quality_kernel<bf16_t>), dim3((unsigned)blocks), dim3(C2M_FS_THREADS), 0, s,
+                           (const bf16_t*)pred, target, valid, regions, T, (int)plane, sp[0], sp[1], sp[2], st[0], st[1], st[2],
                            (unsigned)fs_tiles(H, W), partial);
     C2M_LAUNCH_CHECK();
-    hipLaunchKernelGGL(flow_score_reduce_kernel, dim3((unsigned)frames), dim3(C2M_FS_RED_THREADS), 0, s, partial,
-                       (int)fs_tiles(H, W), C2M_FS_ROWS * C2M_FQ_COLS, C2M_FQ_COLS, C2M_FQ_COLS, out);
-    return (int)hipGetLastError();
+    return score_reduce<8, 128, C2M_FQ_COLS>(partial, frames, fs_tiles(H, W), C2M_FQ_COLS, out, s);
 }
 
 template <typename T, int C>
@@ -372,11 +325,11 @@ C2M_API int c2m_flow_consistency(const float* flow_ab, const void* a, const void
         return (int)hipErrorInvalidValue;
     const long frames = (long)B * T, plane = (long)H * W;
     if (frames == 0) return 0;
-    if (plane > 0x7fffffffL || frames > 0x7fffffffL || frames * fs_tiles(H, W) > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    if (!score_sizes_ok(frames, plane, fs_tiles(H, W))) return (int)hipErrorInvalidValue;
     const long blocks = frames * fs_tiles(H, W);
     const bool maps = photo != nullptr || fb != nullptr || inconsistent != nullptr;
     if (flow_ab == nullptr || a == nullptr || b == nullptr || out == nullptr || workspace == nullptr ||
-        workspace_bytes < fs_workspace_bytes(B, T, H, W, C2M_FC_COLS) ||
+        workspace_bytes < c2m_flow_consistency_workspace_bytes(B, T, H, W) ||
         (maps && (photo == nullptr || fb == nullptr || inconsistent == nullptr)))
         return (int)hipErrorInvalidValue;
     FsStrides st;
@@ -396,10 +349,8 @@ C2M_API int c2m_flow_consistency(const float* flow_ab, const void* a, const void
                                 fb, inconsistent, partial, s);                                                               \
     } while (0)
     if (image_dt == 0) C2M_FC_GO(float);
-    else C2M_FC_GO(FsBf16);
+    else C2M_FC_GO(bf16_t);
 #undef C2M_FC_GO
     C2M_LAUNCH_CHECK();
-    hipLaunchKernelGGL(flow_score_reduce_kernel, dim3((unsigned)frames), dim3(C2M_FS_RED_THREADS), 0, s, partial, (int)tiles,
-                       C2M_FS_ROWS * C2M_FC_COLS, C2M_FC_COLS, flow_ba != nullptr ? C2M_FC_COLS : 4, out);
-    return (int)hipGetLastError();
+    return score_reduce<8, 128, C2M_FC_COLS>(partial, frames, tiles, flow_ba != nullptr ? C2M_FC_COLS : 4, out, s);
 }

@@ -15,13 +15,14 @@
 //   rows     the five horizontal 11-tap sums of every staged row at the TW tile columns -> LDS, fp64 [5][26][32];
 //   columns  each thread owns two vertically adjacent centres of one column: twelve rows of the five sums from LDS, the eleven
 //            weights applied twice, S for both.
-// Then nine rows (whole frame, region bits 0..7) of (n_pixels, sse, n_windows, ssim_sum) are reduced in a fixed order -- wave
-// shuffles, then the four waves in index order from LDS -- into partial[block][9][4]; a second kernel, one workgroup per
-// frame, adds the partials in a fixed order.  No atomics: the result is bit-repeatable.
+// Then nine rows (whole frame, region bits 0..7) of (n_pixels, sse, n_windows, ssim_sum) go through the reduction of
+// score_rows.h -- wave shuffles, the four waves in index order into partial[block][9][4], then score_reduce_kernel<16, 64>, one
+// workgroup per frame.  No atomics: the result is bit-repeatable.
 // LDS per workgroup: 33,280 (row sums) + 8,736 (staging; 6,552 for uint8 x 3) + 1,152 (reduction) = 43,168 bytes at most:
-// three workgroups per CU.
+// three workgroups per CU.  The reduce kernel holds 16 x 64 x 8 = 8,192 bytes (36 of the 64 slots are used), one workgroup per
+// frame: its occupancy is not limited by it.
 #include <initializer_list>
-#include "common.h"
+#include "score_rows.h"
 
 #define C2M_Q_TH 16
 #define C2M_Q_TW 32
@@ -30,17 +31,9 @@
 #define C2M_Q_SR (C2M_Q_TH + 2 * C2M_Q_R)      // staged rows, 26
 #define C2M_Q_SC (C2M_Q_TW + 2 * C2M_Q_R)      // staged columns, 42
 #define C2M_Q_THREADS 256
-#define C2M_Q_ROWS 9                           // whole frame + 8 region bits
-#define C2M_Q_VALS (C2M_Q_ROWS * 4)
-#define C2M_Q_RED_THREADS 1024
+#define C2M_Q_COLS 4                           // n_pixels, sse, n_windows, ssim_sum
 
 struct QualityWeights { double w[C2M_Q_TAPS]; };
-
-struct QBf16 { uint16_t bits; };
-
-__device__ __forceinline__ double q_val(float v) { return (double)v; }
-__device__ __forceinline__ double q_val(QBf16 v) { return (double)__uint_as_float((uint32_t)v.bits << 16); }
-__device__ __forceinline__ double q_val(uint8_t v) { return (double)(int)v; }
 
 template <typename T> struct QIsU8 { static constexpr bool value = false; };
 template <> struct QIsU8<uint8_t> { static constexpr bool value = true; };
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
     constexpr int CS = U8 ? C : 1;                                   // channels held by one staging
     __shared__ T stage[2][C2M_Q_SR * C2M_Q_SC * CS];
     __shared__ double mom[5][C2M_Q_SR * C2M_Q_TW];
-    __shared__ double red[C2M_Q_THREADS / 64][C2M_Q_VALS];
+    __shared__ double red[C2M_Q_THREADS / 64][C2M_SCORE_ROWS * C2M_Q_COLS];
 
     const int tid = threadIdx.x;
     const unsigned tiles = (unsigned)tiles_x * tiles_y;
@@ -107,7 +100,7 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
 #pragma unroll
             for (int k = 0; k < C2M_Q_TAPS; ++k) {
-                const double x = q_val(sx[k * CS]), y = q_val(sy[k * CS]), w = wt.w[k];
+                const double x = score_val(sx[k * CS]), y = score_val(sy[k * CS]), w = wt.w[k];
                 a0 = fma(w, x, a0);
                 a1 = fma(w, y, a1);
                 a2 = fma(w, x * x, a2);
@@ -125,13 +118,13 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
         {
             const int i0 = ((2 * rp + C2M_Q_R) * C2M_Q_SC + col + C2M_Q_R) * CS + ch, i1 = i0 + C2M_Q_SC * CS;
             if (U8) {
-                const int d0 = (int)q_val(stage[0][i0]) - (int)q_val(stage[1][i0]);
-                const int d1 = (int)q_val(stage[0][i1]) - (int)q_val(stage[1][i1]);
+                const int d0 = (int)score_val(stage[0][i0]) - (int)score_val(stage[1][i0]);
+                const int d1 = (int)score_val(stage[0][i1]) - (int)score_val(stage[1][i1]);
                 isse0 += d0 * d0;
                 isse1 += d1 * d1;
             } else {
-                const double d0 = q_val(stage[0][i0]) - q_val(stage[1][i0]);       // exact
-                const double d1 = q_val(stage[0][i1]) - q_val(stage[1][i1]);
+                const double d0 = score_val(stage[0][i0]) - score_val(stage[1][i0]);       // exact
+                const double d1 = score_val(stage[0][i1]) - score_val(stage[1][i1]);
                 sse0 += d0 * d0;
                 sse1 += d1 * d1;
             }
@@ -176,9 +169,9 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
         if (in1) rg1 = regions[o + W];
     }
     const int lane = tid & 63, wave = tid >> 6;
-    const int nrows = regions != nullptr ? C2M_Q_ROWS : 1;
+    const int nrows = regions != nullptr ? C2M_SCORE_ROWS : 1;
     for (int k = 0; k < nrows; ++k) {
-        const bool m0 = in0 && (k == 0 || ((rg0 >> (k - 1)) & 1u)), m1 = in1 && (k == 0 || ((rg1 >> (k - 1)) & 1u));
+        const bool m0 = in0 && C2M_SCORE_ROW_HAS(k, rg0), m1 = in1 && C2M_SCORE_ROW_HAS(k, rg1);
         int cnt = (int)m0 + (int)m1 + (((int)(m0 && ok0) + (int)(m1 && ok1)) << 16);      // pixels | windows << 16
         double e = (m0 ? sse0 : 0.0) + (m1 ? sse1 : 0.0);
         double s = (m0 ? ssim0 : 0.0) + (m1 ? ssim1 : 0.0);
@@ -187,46 +180,21 @@ __global__ __launch_bounds__(C2M_Q_THREADS) void frame_quality_kernel(
         e = wave_sum(e);
         s = wave_sum(s);
         if (lane == 0) {
-            red[wave][k * 4 + 0] = (double)(cnt & 0xffff);
-            red[wave][k * 4 + 1] = e;
-            red[wave][k * 4 + 2] = (double)(cnt >> 16);
-            red[wave][k * 4 + 3] = s;
+            double* r = &red[wave][k * C2M_Q_COLS];
+            r[0] = (double)(cnt & 0xffff);
+            r[1] = e;
+            r[2] = (double)(cnt >> 16);
+            r[3] = s;
         }
     }
     __syncthreads();
-    if (tid < C2M_Q_VALS) {
-        double a = 0.0;
-        if (tid < nrows * 4) a = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        partial[(long)blockIdx.x * C2M_Q_VALS + tid] = a;
-    }
+    score_store_partial<C2M_Q_COLS>(red, nrows, partial);
 }
 
-// One workgroup per frame: value v = tid & 63 (< 36), slice s = tid >> 6 adds the tiles s, s + 16, ... in order; the 16 slices
-// are then added in index order.
-__global__ __launch_bounds__(C2M_Q_RED_THREADS) void frame_quality_reduce_kernel(const double* __restrict__ partial, int tiles,
-                                                                                  double* __restrict__ out) {
-    __shared__ double acc[C2M_Q_RED_THREADS / 64][C2M_Q_VALS];
-    const int v = threadIdx.x & 63, s = threadIdx.x >> 6;
-    const double* __restrict__ p = partial + (long)blockIdx.x * tiles * C2M_Q_VALS;
-    if (v < C2M_Q_VALS) {
-        double a = 0.0;
-#pragma unroll 4
-        for (int i = s; i < tiles; i += C2M_Q_RED_THREADS / 64) a += p[(long)i * C2M_Q_VALS + v];
-        acc[s][v] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x < C2M_Q_VALS) {
-        double a = 0.0;
-        for (int i = 0; i < C2M_Q_RED_THREADS / 64; ++i) a += acc[i][threadIdx.x];
-        out[(long)blockIdx.x * C2M_Q_VALS + threadIdx.x] = a;
-    }
-}
-
-static long q_blocks(long frames, int H, int W) { return frames * c2m_cdiv(H, C2M_Q_TH) * c2m_cdiv(W, C2M_Q_TW); }
+static long q_tiles(int H, int W) { return (long)c2m_cdiv(H, C2M_Q_TH) * c2m_cdiv(W, C2M_Q_TW); }
 
 C2M_API long c2m_frame_quality_workspace_bytes(int B, int T, int H, int W) {
-    if (B < 0 || T < 0 || H < 1 || W < 1) return -1;
-    return q_blocks((long)B * T, H, W) * C2M_Q_VALS * (long)sizeof(double);
+    return score_workspace_bytes(B, T, H, W, q_tiles(H, W), C2M_Q_COLS);
 }
 
 template <typename T, int C>
@@ -247,10 +215,10 @@ C2M_API int c2m_frame_quality(const void* pred, const void* target, const uint8_
         return (int)hipErrorInvalidValue;
     const long frames = (long)B * T;
     if (frames == 0) return 0;
-    const long blocks = q_blocks(frames, H, W);
-    if (blocks > 0x7fffffffL || frames > 0x7fffffffL || (long)H * W * C > 0x7fffffffL) return (int)hipErrorInvalidValue;
+    if (!score_sizes_ok(frames, (long)H * W * C, q_tiles(H, W))) return (int)hipErrorInvalidValue;
+    const long blocks = frames * q_tiles(H, W);
     if (pred == nullptr || target == nullptr || out == nullptr || workspace == nullptr ||
-        workspace_bytes < blocks * C2M_Q_VALS * (long)sizeof(double))
+        workspace_bytes < c2m_frame_quality_workspace_bytes(B, T, H, W))
         return (int)hipErrorInvalidValue;
     // a frame's elements must lie inside the strides the caller states: dense inner dims, non-overlapping frames
     const long plane = (long)H * W * (form == 2 ? C : 1);
@@ -271,11 +239,9 @@ C2M_API int c2m_frame_quality(const void* pred, const void* target, const uint8_
                                (unsigned)blocks, wt, L, partial, s);                                                         \
     } while (0)
     if (form == 0) C2M_Q_GO(float);
-    else if (form == 1) C2M_Q_GO(QBf16);
+    else if (form == 1) C2M_Q_GO(bf16_t);
     else C2M_Q_GO(uint8_t);
 #undef C2M_Q_GO
     C2M_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_quality_reduce_kernel, dim3((unsigned)frames), dim3(C2M_Q_RED_THREADS), 0, s, partial,
-                       tiles_x * tiles_y, out);
-    return (int)hipGetLastError();
+    return score_reduce<16, 64, C2M_Q_COLS>(partial, frames, q_tiles(H, W), C2M_Q_COLS, out, s);
 }

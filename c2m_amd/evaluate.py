@@ -200,6 +200,40 @@ def _div(a, b):
     return torch.where(b > 0, a / torch.where(b > 0, b, torch.ones_like(b)), torch.full_like(a, _NAN))
 
 
+def _region_count(region_names):
+    k = 8 if region_names is None else len(region_names)
+    if not 0 <= k <= 8:
+        raise ValueError("a region byte has 8 bits")
+    return k
+
+
+def _split_rows(values, k):
+    """{key: [..., 9]} -> {key: the frame's [...], "region_" + key: [..., k]}."""
+    out = {}
+    for key, v in values.items():
+        out[key] = v[..., 0]
+        out["region_" + key] = v[..., 1:1 + k]
+    return out
+
+
+def _mean(v, dim):
+    """Mean over `dim` of the finite entries, NaN where there is none."""
+    ok = torch.isfinite(v)
+    return _div(torch.where(ok, v, torch.zeros_like(v)).sum(dim), ok.sum(dim).double())
+
+
+def _row_keys(k, names):
+    """The result keys of quantity k, one per row: k for the frame, <region>_k for the regions."""
+    return [k if i == 0 else f"{name}_{k}" for i, name in enumerate(names)]
+
+
+def _put_rows(out, k, names, overall, per_t, suffix=""):
+    """out[<key><suffix>] and out[<key><suffix>_per_frame] for every row key of k, from overall [1+R] and per_t [T,1+R]."""
+    for i, key in enumerate(_row_keys(k, names)):
+        out[key + suffix] = float(overall[i])
+        out[key + suffix + "_per_frame"] = per_t[:, i].tolist()
+
+
 def quality_from_sums(sums, channels, data_range, region_names=None):
     """The host arithmetic of frame_quality: sums [B,T,9,4] float64 (n_pixels, sse, n_windows, ssim_sum) -> the result dict."""
     sums = torch.as_tensor(sums, dtype=torch.float64)
@@ -209,12 +243,8 @@ def quality_from_sums(sums, channels, data_range, region_names=None):
     with_err = sse > 0
     psnr = torch.where(with_err, 10.0 * torch.log10(L2 / torch.where(with_err, mse_raw, torch.ones_like(mse_raw))),
                        torch.where(n > 0, torch.full_like(sse, float("inf")), torch.full_like(sse, _NAN)))
-    mse, ssim = mse_raw / L2, _div(ss, nw)
-    k = 8 if region_names is None else len(region_names)
-    if not 0 <= k <= 8:
-        raise ValueError("a region byte has 8 bits")
-    return {"mse": mse[..., 0], "psnr": psnr[..., 0], "ssim": ssim[..., 0], "region_mse": mse[..., 1:1 + k],
-            "region_psnr": psnr[..., 1:1 + k], "region_ssim": ssim[..., 1:1 + k], "region_pixels": n[..., 1:1 + k]}
+    k = _region_count(region_names)
+    return dict(_split_rows({"mse": mse_raw / L2, "psnr": psnr, "ssim": _div(ss, nw)}, k), region_pixels=n[..., 1:1 + k])
 
 
 def frame_quality(pred, target, regions=None, region_names=None):
@@ -250,22 +280,14 @@ class QualityScore:
                 raise ValueError("results with different numbers of predicted frames")
             self.rows[k].append(row)
 
-    @staticmethod
-    def _mean(v, dim):
-        ok = torch.isfinite(v)
-        return _div(torch.where(ok, v, torch.zeros_like(v)).sum(dim), ok.sum(dim).double())
-
     def result(self):
         names = ("frame",) + self.region_names
         out = {}
         for k in self._KEYS:
             v = torch.cat(self.rows[k], 0) if self.rows[k] else torch.zeros(0, 0, len(names), dtype=torch.float64)
-            overall, per_t = self._mean(v, (0, 1)), self._mean(v, 0)                  # [1+R], [T,1+R]
-            for i, name in enumerate(names):
-                key = k if i == 0 else f"{name}_{k}"
-                out[key] = float(overall[i])
-                out[key + "_per_frame"] = per_t[:, i].tolist()
-                if k == "psnr":
+            _put_rows(out, k, names, _mean(v, (0, 1)), _mean(v, 0))                   # [1+R], [T,1+R]
+            if k == "psnr":
+                for i, key in enumerate(_row_keys(k, names)):
                     out[key.replace("psnr", "psnr_identical")] = int(torch.isinf(v[..., i]).sum())
         out["frames"] = int(sum(r.shape[0] * r.shape[1] for r in self.rows["mse"]))
         return out
@@ -370,38 +392,71 @@ def semantic_scores(confusion):
     return {"mIoU": float(100 * miou), "fwIoU": float(100 * fiou), "mACC": float(100 * macc), "pACC": float(100 * pacc)}
 
 
+def _pq_zero(C, **extra):
+    """An empty tally of panoptic-quality counts over C classes, plus the caller's own entries."""
+    return {"tp": np.zeros(C, np.int64), "fp": np.zeros(C, np.int64), "fn": np.zeros(C, np.int64),
+            "iou": np.zeros(C, np.float64), **extra}
+
+
+def _pq_host(result, keys, what, max_pairs, call):
+    """The entries `keys` of a map_quality / tube_quality result as numpy arrays; refuses one with an overflow flag."""
+    host = {k: (result[k].cpu().numpy() if isinstance(result[k], torch.Tensor) else np.asarray(result[k]))
+            for k in tuple(keys) + ("overflow",)}
+    over = host.pop("overflow").astype(bool)
+    if over.any():
+        raise ValueError(f"{int(over.sum())} {what} had more distinct segment pairs than max_pairs={max_pairs}: "
+                         f"their counts are incomplete; call {call} with a larger max_pairs")
+    return host
+
+
+def _pq_tally(host, keys, lead, tallies_of):
+    """Adds host[k] for k in keys, the `lead` leading axes flattened to rows, into every tally of tallies_of(i), one row at a
+    time in arrival order (iou: one float64 addition per class and row).  Returns the number of rows."""
+    rows = {k: host[k].reshape((-1,) + host[k].shape[lead:]) for k in keys}
+    rows["iou"] = rows["iou"].astype(np.float64)
+    for i in range(len(rows["tp"])):
+        for acc in tallies_of(i):
+            for k in keys:
+                acc[k] += rows[k][i]
+    return len(rows["tp"])
+
+
+def _pq_scores(acc, num_classes, things):
+    """PQStat.pq_average of a tally over All / Things / Stuff, and All's per-class values as "per_class"."""
+    out = {}
+    for name, isthing in _PQ_GROUPS:
+        classes = [c for c in range(num_classes) if isthing is None or (c in things) == isthing]
+        out[name], per_class = pq_average(acc["tp"], acc["fp"], acc["fn"], acc["iou"], classes)
+        if name == "All":
+            out["per_class"] = per_class
+    return out
+
+
+def _pq_params(who, params):
+    """(params, num_classes, max_pairs, things) of a MapScore / TubeScore constructor."""
+    p = _map_params(who, params)
+    return p, int(p["num_classes"]), int(p["max_pairs"]), tuple(sorted(set(int(c) for c in p["thing_list"])))
+
+
 class MapScore:
     """Sums of map_quality results over a dataset and the reference's averages of them (cityscapesscripts' PQStat.pq_average /
     average_pq and Panoptic-DeepLab's SemanticEvaluator.evaluate): overall and, where the results had a frame axis [B,T], per
     predicted-frame index.  The per-frame values are added in the order they arrive."""
 
+    _KEYS = ("tp", "fp", "fn", "iou", "confusion")
+
     def __init__(self, **params):
-        p = _map_params("MapScore", params)
-        self.num_classes, self.max_pairs = int(p["num_classes"]), int(p["max_pairs"])
-        self.things = tuple(sorted(set(int(c) for c in p["thing_list"])))
-        self.params = p
+        self.params, self.num_classes, self.max_pairs, self.things = _pq_params("MapScore", params)
         self.per_t = None                                    # None until the first update; [] for results without a frame axis
         self.total = self._zero()
         self.frames = 0
 
     def _zero(self):
-        C = self.num_classes
-        return {"tp": np.zeros(C, np.int64), "fp": np.zeros(C, np.int64), "fn": np.zeros(C, np.int64),
-                "iou": np.zeros(C, np.float64), "confusion": np.zeros((C + 1, C + 1), np.int64)}
-
-    @staticmethod
-    def _add(acc, row):
-        for k in acc:
-            acc[k] += row[k]                                 # iou: one float64 addition per class and frame, in arrival order
+        return _pq_zero(self.num_classes, confusion=np.zeros((self.num_classes + 1,) * 2, np.int64))
 
     def update(self, result):
         C = self.num_classes
-        host = {k: (result[k].cpu().numpy() if isinstance(result[k], torch.Tensor) else np.asarray(result[k]))
-                for k in ("tp", "fp", "fn", "iou", "confusion", "overflow")}
-        over = host.pop("overflow").astype(bool)
-        if over.any():
-            raise ValueError(f"{int(over.sum())} frame(s) had more distinct segment pairs than max_pairs={self.max_pairs}: "
-                             f"their counts are incomplete; call map_quality with a larger max_pairs")
+        host = _pq_host(result, self._KEYS, "frame(s)", self.max_pairs, "map_quality")
         lead = host["tp"].shape[:-1]
         if host["tp"].shape[-1] != C or host["confusion"].shape[-2:] != (C + 1, C + 1) or len(lead) not in (1, 2):
             raise ValueError(f"result of {host['tp'].shape[-1]} classes with leading axes {lead}; the score has {C} classes and "
@@ -411,24 +466,11 @@ class MapScore:
             self.per_t = [self._zero() for _ in range(T)]
         if len(self.per_t) != T:
             raise ValueError("results with different numbers of predicted frames")
-        rows = {k: v.reshape((-1,) + v.shape[len(lead):]) for k, v in host.items()}
-        rows["iou"] = rows["iou"].astype(np.float64)
-        for i in range(rows["tp"].shape[0]):
-            row = {k: v[i] for k, v in rows.items()}
-            self._add(self.total, row)
-            if T:
-                self._add(self.per_t[i % T], row)
-            self.frames += 1
+        self.frames += _pq_tally(host, self._KEYS, len(lead),
+                                 lambda i: (self.total, self.per_t[i % T]) if T else (self.total,))
 
     def _scores(self, acc):
-        out = {}
-        for name, isthing in _PQ_GROUPS:
-            classes = [c for c in range(self.num_classes) if isthing is None or (c in self.things) == isthing]
-            out[name], per_class = pq_average(acc["tp"], acc["fp"], acc["fn"], acc["iou"], classes)
-            if name == "All":
-                out["per_class"] = per_class
-        out.update(semantic_scores(acc["confusion"]))
-        return out
+        return dict(_pq_scores(acc, self.num_classes, self.things), **semantic_scores(acc["confusion"]))
 
     def result(self):
         out = self._scores(self.total)
@@ -517,17 +559,9 @@ class TubeScore:
     Things / Stuff; `vpq` is the mean over k of the per-k PQ.  With ids, the mean id_iou over the entries >= 0 per k."""
 
     def __init__(self, **params):
-        p = _map_params("TubeScore", params)
-        self.num_classes, self.max_pairs = int(p["num_classes"]), int(p["max_pairs"])
-        self.things = tuple(sorted(set(int(c) for c in p["thing_list"])))
-        self.params = p
+        self.params, self.num_classes, self.max_pairs, self.things = _pq_params("TubeScore", params)
         self.total = None                                    # {k: sums}, fixed by the first update
         self.windows = 0
-
-    def _zero(self):
-        C = self.num_classes
-        return {"tp": np.zeros(C, np.int64), "fp": np.zeros(C, np.int64), "fn": np.zeros(C, np.int64),
-                "iou": np.zeros(C, np.float64), "windows": 0, "id_sum": 0.0, "id_n": 0}
 
     def update(self, result):
         C = self.num_classes
@@ -537,25 +571,18 @@ class TubeScore:
             raise ValueError(f"results with different window lengths: {sorted(self.total)} and {sorted(result)}")
         host = {}
         for k, r in result.items():
-            h = {n: (r[n].cpu().numpy() if isinstance(r[n], torch.Tensor) else np.asarray(r[n]))
-                 for n in _TUBE_KEYS + ("overflow",) + (("id_iou",) if "id_iou" in r else ())}
-            over = h["overflow"].astype(bool)
-            if over.any():
-                raise ValueError(f"{int(over.sum())} window(s) of {int(k)} frame(s) had more distinct segment pairs than max_pairs="
-                                 f"{self.max_pairs}: their counts are incomplete; call tube_quality with a larger max_pairs")
+            h = _pq_host(r, _TUBE_KEYS + (("id_iou",) if "id_iou" in r else ()), f"window(s) of {int(k)} frame(s)",
+                         self.max_pairs, "tube_quality")
             if h["tp"].ndim != 3 or h["tp"].shape[-1] != C:
                 raise ValueError(f"result of shape {h['tp'].shape} for k={int(k)}; the score has {C} classes and takes [B,T-k+1,C]")
             host[int(k)] = h
         if self.total is None:
-            self.total = {k: self._zero() for k in host}
-        for k, h in host.items():
+            self.total = {k: _pq_zero(C, windows=0, id_sum=0.0, id_n=0) for k in host}
+        for k, h in host.items():                            # every k was checked before the first row is added
             acc = self.total[k]
-            rows = {n: h[n].reshape(-1, C) for n in _TUBE_KEYS}
-            for i in range(rows["tp"].shape[0]):             # iou: one float64 addition per class and window, in arrival order
-                for n in _TUBE_KEYS:
-                    acc[n] += rows[n][i]
-            acc["windows"] += rows["tp"].shape[0]
-            self.windows += rows["tp"].shape[0]
+            n = _pq_tally(h, _TUBE_KEYS, 2, lambda i: (acc,))
+            acc["windows"] += n
+            self.windows += n
             if "id_iou" in h:
                 v = h["id_iou"].astype(np.float64).reshape(-1)
                 for x in v[v >= 0]:
@@ -565,12 +592,7 @@ class TubeScore:
     def result(self):
         out = {"windows": self.windows, "per_k": {}}
         for k, acc in sorted((self.total or {}).items()):
-            s = {"windows": acc["windows"]}
-            for name, isthing in _PQ_GROUPS:
-                classes = [c for c in range(self.num_classes) if isthing is None or (c in self.things) == isthing]
-                s[name], per_class = pq_average(acc["tp"], acc["fp"], acc["fn"], acc["iou"], classes)
-                if name == "All":
-                    s["per_class"] = per_class
+            s = {"windows": acc["windows"], **_pq_scores(acc, self.num_classes, self.things)}
             s["id_iou"] = acc["id_sum"] / acc["id_n"] if acc["id_n"] else None
             s["id_n"] = acc["id_n"]
             out["per_k"][k] = s
@@ -602,7 +624,7 @@ class TubeScore:
 FLOW_REGIONS = ("object", "background", "boundary", "occluded", "slow", "medium", "fast")
 FLOW_QUALITY_COLUMNS = ("n", "n_nonfinite", "sum_epe", "sum_e2", "sum_mag", "sum_ae", "n_out", "n_gt1", "n_gt3", "n_gt5")
 FLOW_CONSISTENCY_COLUMNS = ("n", "n_inside", "sum_photo", "sum_photo2", "sum_fb", "n_incons", "sum_photo_cons")
-FLOW_SCORE_ROWS = 9         # every counted pixel, then region bits 0..7
+FLOW_SCORE_ROWS = ops.SCORE_ROWS                # every counted pixel, then region bits 0..7
 _FLOW_FLOATS = (torch.float32, torch.bfloat16)
 
 
@@ -761,21 +783,6 @@ def flow_consistency_sums(flow_ab, a, b, flow_ba=None, regions=None, alpha1=0.01
                                           B, C, T, H, W, (ctypes.c_long * 12)(*strides), float(alpha1), float(alpha2), *mp,
                                           ops._p(work), nbytes, ops._p(out), ops._stream()), "flow_consistency")
     return (out, m) if maps else out
-
-
-def _region_count(region_names):
-    k = 8 if region_names is None else len(region_names)
-    if not 0 <= k <= 8:
-        raise ValueError("a region byte has 8 bits")
-    return k
-
-
-def _split_rows(values, k):
-    out = {}
-    for key, v in values.items():
-        out[key] = v[..., 0]
-        out["region_" + key] = v[..., 1:1 + k]
-    return out
 
 
 def flow_quality_from_sums(sums, region_names=None):
@@ -940,13 +947,8 @@ class FlowScore:
         pooled, pooled_t, each = self._flat(v.sum((0, 1))), self._flat(v.sum(0)), self._flat(v)
         out = {}
         for k in self.keys:
-            mean, mean_t = QualityScore._mean(each[k], (0, 1)), QualityScore._mean(each[k], 0)
-            for i, name in enumerate(names):
-                key = k if i == 0 else f"{name}_{k}"
-                out[key] = float(pooled[k][i])
-                out[key + "_per_frame"] = pooled_t[k][:, i].tolist()
-                out[key + "_mean"] = float(mean[i])
-                out[key + "_mean_per_frame"] = mean_t[:, i].tolist()
+            _put_rows(out, k, names, pooled[k], pooled_t[k])
+            _put_rows(out, k, names, _mean(each[k], (0, 1)), _mean(each[k], 0), "_mean")
         out["pairs"] = int(v.shape[0] * v.shape[1])
         return out
 

@@ -3054,7 +3054,8 @@ def detail_warp(frame_u8, generated, warped, flow, occ=None, ids=None, occ_thres
 # ====================================================================================== frame quality (csrc/quality.hip)
 QUALITY_TAPS = 11
 QUALITY_SIGMA = 1.5
-QUALITY_ROWS = 9            # the whole frame, then region bits 0..7
+SCORE_ROWS = 9              # csrc/score_rows.h: the whole frame, then region bits 0..7; every score kernel writes [..., 9, K]
+QUALITY_ROWS = SCORE_ROWS
 
 
 def quality_weights():
@@ -3667,7 +3668,7 @@ def match_detections(dets, kept, index, roi, x, batch, scale, size):
 PANOPTIC_MAX_TOP_K = 1024       # c2m_panoptic_max_top_k(): the grouping kernel stages a frame's centres whole in LDS
 _PanopticPlan = collections.namedtuple(
     "_PanopticPlan", "form N C H W things threshold nms_kernel top_k label_divisor stuff_area ignore_label")
-_PANOPTIC_TABLES = {}
+_PANOPTIC_CLASSES = {}
 
 
 def _panoptic_plan(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k):
@@ -3726,13 +3727,9 @@ def _panoptic_plan(semantic, center, offset, thing_list, label_divisor, stuff_ar
 def _panoptic_tables(things, device):
     """Device tables of a thing list: uint8 [256] (0: no thing, else 1 + position) and int32 [len] (the classes, ascending)."""
     key = (things, device.index)
-    if key not in _PANOPTIC_TABLES:
-        tab = np.zeros(256, np.uint8)
-        for i, c in enumerate(things):
-            tab[c] = i + 1
-        _PANOPTIC_TABLES[key] = (torch.from_numpy(tab).to(device),
-                                 torch.tensor(list(things) or [0], dtype=torch.int32, device=device))
-    return _PANOPTIC_TABLES[key]
+    if key not in _PANOPTIC_CLASSES:
+        _PANOPTIC_CLASSES[key] = torch.tensor(list(things) or [0], dtype=torch.int32, device=device)
+    return _thing_table(things, device), _PANOPTIC_CLASSES[key]
 
 
 def panoptic_maps(semantic, center, offset, thing_list, label_divisor, stuff_area, ignore_label, threshold, nms_kernel, top_k):

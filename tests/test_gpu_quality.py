@@ -28,7 +28,9 @@ CASES = [("f32", 3, 1, 1, 11, 11), ("f32", 1, 1, 1, 11, 12), ("f32", 3, 1, 1, 12
          ("f32", 1, 2, 3, 15, 33), ("f32", 3, 2, 3, 16, 32), ("f32", 3, 1, 1, 17, 31), ("f32", 1, 1, 1, 33, 65),
          ("f32", 3, 1, 1, 15, 65), ("f32", 1, 2, 3, 33, 31),
          ("u8", 3, 2, 3, 17, 33), ("u8", 3, 1, 1, 33, 65), ("u8", 3, 1, 1, 16, 31), ("u8", 1, 2, 3, 15, 33), ("u8", 1, 1, 1, 32, 64),
-         ("bf16", 3, 2, 3, 17, 33), ("bf16", 1, 1, 1, 16, 65)]
+         ("bf16", 3, 2, 3, 17, 33), ("bf16", 1, 1, 1, 16, 65),
+         # more tiles than the reduce kernel has slices (16): 2 x 9 = 18 tiles, slices 0 and 1 add two; 3 x 12 = 36, slices 0..3 three
+         ("f32", 1, 1, 1, 17, 257), ("u8", 3, 1, 1, 33, 353)]
 _cases = {}
 
 
